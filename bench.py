@@ -34,9 +34,15 @@ acks per follower per round, 1,128 B/group) is reported as
 `reference_width_bytes_per_launch` only. `copy_f4_GBs` is tools/hbm_calib's
 float4 copy on the same box (achievable HBM).
 
-Beside the headline (rank 0, N = 1): `host_path` times gr_step with host records
-(the C-ABI call a Go step worker makes, PCIe-inclusive), and `cpu_baseline`
-follows BASELINE.md's CPU protocol on bounded samples.
+A plain run (--gpus 1 --steps N --warmup W) sets up, warms up, times the N
+passes and prints the headline line (`value`, `ms_per_step`, the workload's
+description). --dump-outputs DIR also writes what the last timed pass left
+(dump_outputs below). Everything else runs only with --full: the roofline block
+(the same passes once more under per-kernel HIP events, the PMC and configs
+records under profiles/, tools/hbm_calib's copy), the build record, and beside
+the headline (rank 0, N = 1) `host_path`, which times gr_step with host records
+(the C-ABI call a Go step worker makes, PCIe-inclusive), and `cpu_baseline`,
+which follows BASELINE.md's CPU protocol on bounded samples.
 """
 import argparse
 import json
@@ -112,6 +118,13 @@ def parse():
     ap.add_argument("--host-pipeline-partitions", type=int, default=4,
                     help="partitions of the pipelined compact host-path leg (begin/end halves)")
     ap.add_argument("--check", action="store_true", help="verify the final state against a host replay")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline block (per-kernel events over the same passes once more, PMC and "
+                         "configs records, HBM copy calibration), the build record, the host-path legs and the "
+                         "CPU baseline (--host-path / --cpu-baseline choose among them); off: the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed pass left (sampled peer records, "
+                         "results, mailboxes, the device counters) as DIR/<name>.npy, float64")
     return ap.parse_args()
 
 
@@ -449,6 +462,167 @@ def copy_peak_gbs():
         return None
 
 
+DUMP_GROUPS, DUMP_RESULTS, DUMP_TILES = 8192, 4096, 64  # per rank, shared among its banks
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+
+
+def record_columns(a):
+    """A record array as float64 [len(a), columns]: every field but padding, in
+    dtype order, sub-arrays and nested records flattened."""
+    import numpy as np
+    cols = []
+    for name in a.dtype.names:
+        if name == "pad":
+            continue
+        f = a[name]
+        if f.dtype.names:
+            cols.append(record_columns(f.reshape(-1)).reshape(len(a), -1))
+        else:
+            cols.append(f.reshape(len(a), -1).astype(np.float64))
+    return np.concatenate(cols, axis=1)
+
+
+def dump_outputs(pipe, k_last, path, rank, world):
+    """What a caller of the timed path holds after its last pass (k_last), as
+    float64 .npy files under `path` (a fixed, seeded sample: the whole of a
+    1M x 3 run is 2 GB of peer records and 4 GB of mailboxes):
+      state     gr_peer records (gr_sync_peers_to_host) of every replica of
+                DUMP_GROUPS sampled groups, one row per peer (record_columns)
+      results   gr_peer_result records of the last pass (gr_collect_results),
+                the first DUMP_RESULTS peers of every replica block
+      messages  the space the last pass wrote, DUMP_TILES sampled tiles of
+                mailboxes decoded (gr_space_decode): mailbox position, then the
+                gr_message fields from `type` on, one row per message
+      stats     the device counters over the timed passes (abi.Stats order)
+    Banks are concatenated in order; with N > 1 every rank writes <name>_rank<r>."""
+    import numpy as np
+    import torch
+    from dragonboat_amd import abi
+    from dragonboat_amd.engine import decode_space
+    from dragonboat_amd.exchange import TILE_W, pad_positions
+    banks = len(pipe.ex)
+    state, results, messages = [], [], []
+    for b, (ex, eng, spaces) in enumerate(zip(pipe.ex, pipe.engines, pipe.spaces)):
+        rng = np.random.default_rng([20240, b])
+        G, R = ex.G, ex.R
+        g = np.sort(rng.choice(G, min(G, max(1, DUMP_GROUPS // banks)), replace=False))
+        slots = (np.arange(R)[:, None] * G + g[None, :]).reshape(-1).astype(np.uint32)  # replica-major
+        state.append(record_columns(eng.sync_peers(slots)))
+        nres = min(G, max(1, DUMP_RESULTS // banks))
+        results.append(np.concatenate([record_columns(eng.collect_results(nres, first=r * G)) for r in range(R)]))
+        # the out space of pass k_last; its chunks are tiled by TILE_W positions, a
+        # tile's hot bytes then (after every chunk's hot part) its cold bytes: the
+        # sampled tiles, side by side, are a one-chunk space of their own
+        out = spaces[(k_last + 1) % 2] if ex.pingpong else spaces[1]
+        depth, nc = ex.depth, ex.n_chunks
+        tpc = pad_positions(ex.positions) // TILE_W  # tiles per chunk
+        hot_t = eng.hot_chunk_bytes(TILE_W, depth)
+        cold_t = eng.chunk_bytes(TILE_W, depth) - hot_t
+        hot_c = eng.hot_chunk_bytes(ex.positions, depth)
+        cold_c = eng.chunk_bytes(ex.positions, depth) - hot_c
+        assert hot_c == tpc * hot_t and cold_c == tpc * cold_t and eng.hot_tile_bytes(depth) == hot_t
+        tiles = np.sort(rng.choice(nc * tpc, min(nc * tpc, max(1, DUMP_TILES // banks)), replace=False))
+        hot = [out[(t // tpc) * hot_c + (t % tpc) * hot_t:][:hot_t] for t in tiles.tolist()]
+        cold = [out[nc * hot_c + (t // tpc) * cold_c + (t % tpc) * cold_t:][:cold_t] for t in tiles.tolist()]
+        mini = torch.cat(hot + cold).cpu().numpy()
+        assert len(mini) == eng.space_bytes(1, len(tiles) * TILE_W, depth)
+        m = decode_space(mini, 1, len(tiles) * TILE_W, depth)
+        pos = m["peer"].astype(np.int64)  # position in the sample -> position in the space
+        t = tiles[pos // TILE_W]
+        m["peer"] = ((t // tpc) * pad_positions(ex.positions) + (t % tpc) * TILE_W + pos % TILE_W).astype(np.uint32)
+        messages.append(record_columns(m) if len(m) else record_columns(np.zeros(1, abi.MESSAGE))[:0])
+    st = pipe.stats()
+    arrays = {"state": np.concatenate(state), "results": np.concatenate(results),
+              "messages": np.concatenate(messages),
+              "stats": np.array([st[f] for f, _ in abi.Stats._fields_], np.float64)}
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_MAX_BYTES
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + (f"_rank{rank}" if world > 1 else "") + ".npy"), a)
+
+
+def full_report(args, st, tm, G, R, S, banks):
+    """The --full entries of the result line (rank 0): the roofline block from the
+    per-kernel timings `tm` and the device counters `st` of the timed passes, the
+    configs record and the build record."""
+    passes = max(1, tm["passes"])
+    kavg = tm["fast_ms"] / passes  # the dominant kernel, HIP events on the pass's stream
+    gavg = tm["general_ms"] / passes
+    # SURVEY.md §8d's unit: one group-round (R-1 acks in, quorum commit, R-1
+    # Replicates out, R-1 follower matches) = B_round(R) bytes at reference field
+    # widths; a launch processes one group-round per leader commit.
+    rounds = st["leader_commits"] / (args.steps * banks)  # per launch (one bank's pass)
+    canon = b_round(R) * rounds  # SURVEY.md 8d canonical bytes per launch (reference widths)
+    canon_achieved = canon / (kavg * 1e-3) / 1e9
+    alg = ENCODED_ROUND_BYTES.get(R, b_round(R)) * rounds  # algorithmic bytes per launch (this rank)
+    achieved = alg / (kavg * 1e-3) / 1e9
+    refw = reference_width_bytes(st, G, R, args.steps) / (args.steps * banks)
+    traffic = None
+    pmc = os.path.join(ROOT, "profiles", "pmc_latest.json")
+    if os.path.exists(pmc):  # tools/profile.sh: calibrated FETCH_SIZE + WRITE_SIZE of this kernel
+        try:
+            from dragonboat_amd.build import source_digest
+            rec = json.load(open(pmc))
+            if rec.get("groups") == G and rec.get("replicas") == R and \
+                    rec.get("source_digest") == source_digest():  # measured on this very kernel
+                traffic = rec.get("hbm_bytes_per_launch")
+        except (OSError, ValueError):
+            traffic = None
+    copy_gbs = copy_peak_gbs()
+    traffic_gbs = traffic / (kavg * 1e-3) / 1e9 if traffic else None
+    configs_ev = None  # BASELINE configs 2, 3, 5 on this build (tools/configs_summary.py), never `value`
+    cfg_path = os.path.join(ROOT, "profiles", "configs_latest.json")
+    if os.path.exists(cfg_path):
+        try:
+            from dragonboat_amd.build import source_digest
+            rec = json.load(open(cfg_path))
+            if rec.get("source_digest") == source_digest():
+                configs_ev = {k: {f: v.get(f) for f in ("config", "device_ms_per_pass", "stream_ms_per_pass",
+                                                          "pmc_bytes_per_pass", "canonical_bytes_per_pass",
+                                                          "pmc_over_canonical", "canonical_frac")}
+                              for k, v in rec.get("configs", {}).items()}
+                configs_ev["source"] = "profiles/configs_latest.json (same source digest as this build)"
+        except (OSError, ValueError):
+            configs_ev = None
+    try:  # provenance: the loaded library's build record against this tree's sources
+        from dragonboat_amd.build import build_record, source_digest
+        brec = build_record(os.environ.get("GPURAFT_LIB") or None) or {}
+        build_info = {"lib": brec.get("lib"), "built_from": brec.get("source_digest"),
+                      "tree": source_digest(), "built_at": brec.get("built_at"),
+                      "compiler": brec.get("compiler")}
+        build_info["matches_tree"] = build_info["built_from"] == build_info["tree"]
+    except Exception:  # the record is informational; never fail the bench over it
+        build_info = None
+    return {
+        "build": build_info,
+        "configs_evidence": configs_ev,
+        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                     "kernel": f"lean kernels of one pass (gr_steady_kernel<{S},{R}>; gr_roles_kernel<{S},{R}> too on a pass "
+                               "whose tail plan launches the role instances, none in the steady state)",
+                     "kernel_ms": kavg,
+                     "algorithmic_bytes_per_launch": alg,
+                     "algorithmic_unit": (f"group-round at this engine's encoding, {ENCODED_ROUND_BYTES[R]} B "
+                                          "(bench.py ENCODED_ROUND_BYTES, DESIGN.md 3)" if R in ENCODED_ROUND_BYTES
+                                          else f"group-round, B_round({R}) = {b_round(R)} B (SURVEY.md 8d)"),
+                     "canonical_bytes_per_launch": canon,
+                     "canonical_unit": f"group-round, B_round({R}) = {b_round(R)} B (SURVEY.md 8d, reference "
+                                       "field widths: more bytes than the kernels move)",
+                     "canonical_achieved": canon_achieved,
+                     "canonical_frac": canon_achieved / HBM_PEAK_GBS,
+                     "group_rounds_per_launch": rounds,
+                     "traffic_GBs": traffic_gbs,
+                     "traffic_frac": traffic_gbs / HBM_PEAK_GBS if traffic else None,
+                     "copy_f4_GBs": copy_gbs,
+                     "traffic_frac_of_copy": traffic_gbs / copy_gbs if traffic and copy_gbs else None,
+                     "reference_width_bytes_per_launch": refw,
+                     "reference_width_note": "two Replicates + two acks per follower per round at "
+                                             "reference field widths (1,128 B/group): never used as frac",
+                     "general_kernel_ms": gavg,
+                     "bailed_lanes_per_pass": tm["bailed_lanes"] / passes},
+    }
+
+
 def main():
     args = parse()
     import numpy as np
@@ -526,14 +700,18 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     st = pipe.stats()
-    # Per-kernel durations for the roofline: the same passes once more, outside the
-    # timed region, with HIP events around each kernel (recorded inside the library
-    # on the bank's stream), so the events add nothing to `value`.
-    pipe.timing_begin()
-    for k in range(args.steps):
-        pipe.step(k0 + args.steps + k)
-    pipe.synchronize()
-    tm = pipe.timing_end()
+    if args.dump_outputs:
+        dump_outputs(pipe, k0 + args.steps - 1, args.dump_outputs, rank, world)
+    tm = None
+    if args.full:
+        # Per-kernel durations for the roofline: the same passes once more, outside the
+        # timed region, with HIP events around each kernel (recorded inside the library
+        # on the bank's stream), so the events add nothing to `value`.
+        pipe.timing_begin()
+        for k in range(args.steps):
+            pipe.step(k0 + args.steps + k)
+        pipe.synchronize()
+        tm = pipe.timing_end()
     xbytes = pipe.exchange_bytes_per_pass()
     xbytes_heavy = pipe.exchange_bytes_per_pass(heavy=True)
     banks = len(pipe.ex)
@@ -545,56 +723,8 @@ def main():
         dist.all_reduce(t)
         commits, esc = int(t[0].item()), int(t[1].item())
     value = commits / elapsed
-    passes = max(1, tm["passes"])
-    kavg = tm["fast_ms"] / passes  # the dominant kernel, HIP events on the pass's stream
-    gavg = tm["general_ms"] / passes
     groups_total = G * world
-    # SURVEY.md §8d's unit: one group-round (R-1 acks in, quorum commit, R-1
-    # Replicates out, R-1 follower matches) = B_round(R) bytes at reference field
-    # widths; a launch processes one group-round per leader commit.
-    rounds = st["leader_commits"] / (args.steps * banks)  # per launch (one bank's pass)
-    canon = b_round(R) * rounds  # SURVEY.md 8d canonical bytes per launch (reference widths)
-    canon_achieved = canon / (kavg * 1e-3) / 1e9
-    alg = ENCODED_ROUND_BYTES.get(R, b_round(R)) * rounds  # algorithmic bytes per launch (this rank)
-    achieved = alg / (kavg * 1e-3) / 1e9
-    refw = reference_width_bytes(st, G, R, args.steps) / (args.steps * banks)
     if rank == 0:
-        traffic = None
-        pmc = os.path.join(ROOT, "profiles", "pmc_latest.json")
-        if os.path.exists(pmc):  # tools/profile.sh: calibrated FETCH_SIZE + WRITE_SIZE of this kernel
-            try:
-                from dragonboat_amd.build import source_digest
-                rec = json.load(open(pmc))
-                if rec.get("groups") == G and rec.get("replicas") == R and \
-                        rec.get("source_digest") == source_digest():  # measured on this very kernel
-                    traffic = rec.get("hbm_bytes_per_launch")
-            except (OSError, ValueError):
-                traffic = None
-        copy_gbs = copy_peak_gbs()
-        traffic_gbs = traffic / (kavg * 1e-3) / 1e9 if traffic else None
-        configs_ev = None  # BASELINE configs 2, 3, 5 on this build (tools/configs_summary.py), never `value`
-        cfg_path = os.path.join(ROOT, "profiles", "configs_latest.json")
-        if os.path.exists(cfg_path):
-            try:
-                from dragonboat_amd.build import source_digest
-                rec = json.load(open(cfg_path))
-                if rec.get("source_digest") == source_digest():
-                    configs_ev = {k: {f: v.get(f) for f in ("config", "device_ms_per_pass", "stream_ms_per_pass",
-                                                              "pmc_bytes_per_pass", "canonical_bytes_per_pass",
-                                                              "pmc_over_canonical", "canonical_frac")}
-                                  for k, v in rec.get("configs", {}).items()}
-                    configs_ev["source"] = "profiles/configs_latest.json (same source digest as this build)"
-            except (OSError, ValueError):
-                configs_ev = None
-        try:  # provenance: the loaded library's build record against this tree's sources
-            from dragonboat_amd.build import build_record, source_digest
-            brec = build_record(os.environ.get("GPURAFT_LIB") or None) or {}
-            build_info = {"lib": brec.get("lib"), "built_from": brec.get("source_digest"),
-                          "tree": source_digest(), "built_at": brec.get("built_at"),
-                          "compiler": brec.get("compiler")}
-            build_info["matches_tree"] = build_info["built_from"] == build_info["tree"]
-        except Exception:  # the record is informational; never fail the bench over it
-            build_info = None
         line = {
             "metric": "commit-index updates/sec (1M groups x 3 replicas) + achieved HBM GB/s",
             "value": value,
@@ -622,39 +752,15 @@ def main():
             "exchange_collective": "RCCL all_to_all_single, async on the bank's stream" + (
                 " (one-rank rehearsal: GR_BENCH_COLLECTIVE=1)" if world == 1 else "")
             if placement == "spread" and (world > 1 or collective) else None,
-            "build": build_info,
-            "configs_evidence": configs_ev,
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         "kernel": f"lean kernels of one pass (gr_steady_kernel<{S},{R}>; gr_roles_kernel<{S},{R}> too on a pass "
-                                   "whose tail plan launches the role instances, none in the steady state)",
-                         "kernel_ms": kavg,
-                         "algorithmic_bytes_per_launch": alg,
-                         "algorithmic_unit": (f"group-round at this engine's encoding, {ENCODED_ROUND_BYTES[R]} B "
-                                              "(bench.py ENCODED_ROUND_BYTES, DESIGN.md 3)" if R in ENCODED_ROUND_BYTES
-                                              else f"group-round, B_round({R}) = {b_round(R)} B (SURVEY.md 8d)"),
-                         "canonical_bytes_per_launch": canon,
-                         "canonical_unit": f"group-round, B_round({R}) = {b_round(R)} B (SURVEY.md 8d, reference "
-                                           "field widths: more bytes than the kernels move)",
-                         "canonical_achieved": canon_achieved,
-                         "canonical_frac": canon_achieved / HBM_PEAK_GBS,
-                         "group_rounds_per_launch": rounds,
-                         "traffic_GBs": traffic_gbs,
-                         "traffic_frac": traffic_gbs / HBM_PEAK_GBS if traffic else None,
-                         "copy_f4_GBs": copy_gbs,
-                         "traffic_frac_of_copy": traffic_gbs / copy_gbs if traffic and copy_gbs else None,
-                         "reference_width_bytes_per_launch": refw,
-                         "reference_width_note": "two Replicates + two acks per follower per round at "
-                                                 "reference field widths (1,128 B/group): never used as frac",
-                         "general_kernel_ms": gavg,
-                         "bailed_lanes_per_pass": tm["bailed_lanes"] / passes},
         }
-        if args.host_path == "on" and world == 1:
+        if args.full:
+            line.update(full_report(args, st, tm, G, R, S, banks))
+        if args.full and args.host_path == "on" and world == 1:
             try:
                 line["host_path"] = host_path(args, R, ordinal)
             except Exception as e:  # reported beside the headline, never as `value`
                 line["host_path"] = {"error": str(e)}
-        if args.cpu_baseline == "on" and world == 1:
+        if args.full and args.cpu_baseline == "on" and world == 1:
             try:
                 line["cpu_baseline"] = cpu_baseline(args, R)
             except Exception as e:  # baseline is reported, not required

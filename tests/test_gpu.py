@@ -269,18 +269,57 @@ def test_side_buffer_pack_unpack(gpu):
                        for m in got[keep])
 
 
-def test_bench_runs(gpu):
-    """bench.py's contract on a small population (JSON line with roofline)."""
+def run_bench(*extra):
+    """bench.py on a small population in a process of its own: its result line."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--groups", "20000", "--steps", "5",
-                        "--warmup", "3", "--cpu-baseline", "off"], capture_output=True, text=True, timeout=300)
+                        "--warmup", "3", *extra], capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-3000:]
-    line = json.loads(p.stdout.strip().splitlines()[-1])
+    return json.loads(p.stdout.strip().splitlines()[-1])
+
+
+@pytest.fixture(scope="module")
+def bench_full_dump(gpu, tmp_path_factory):
+    """One --full run that also dumps its outputs: (result line, dump directory)."""
+    d = tmp_path_factory.mktemp("bench_full")
+    return run_bench("--full", "--cpu-baseline", "off", "--dump-outputs", str(d)), d
+
+
+def test_bench_runs(bench_full_dump):
+    """bench.py's contract on a small population (JSON line with roofline)."""
+    line = bench_full_dump[0]
     assert line["value"] > 0 and line["escalations"] == 0
     assert line["roofline"]["achieved"] > 0
+
+
+def test_bench_plain_run_and_outputs(bench_full_dump, tmp_path):
+    """A plain run prints the headline only (no roofline, host path or CPU
+    baseline) and --dump-outputs writes the last timed pass's sampled records:
+    float64 arrays, the same from the plain and the --full run (same arguments,
+    same inputs), with every sampled leader's log one proposal per pass ahead."""
+    full, dfull = bench_full_dump
+    line = run_bench("--dump-outputs", str(tmp_path))
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in line and type(line[key]) is type(full[key])
+    assert line["value"] > 0 and line["ms_per_step"] > 0 and line["steps"] == 5
+    assert not {"roofline", "host_path", "cpu_baseline", "build", "configs_evidence"} & set(line)
+    total = 0
+    for name, cols in (("state", 107), ("results", 26), ("messages", 15), ("stats", None)):
+        a = np.load(tmp_path / (name + ".npy"))
+        assert a.dtype == np.float64 and len(a) > 0 and (cols is None or a.shape[1] == cols)
+        assert np.array_equal(a, np.load(dfull / (name + ".npy"))), name
+        total += a.nbytes
+    assert total <= 64 * 1000 * 1000
+    state = np.load(tmp_path / "state.npy")
+    G = len(state) // 3  # replica-major sample; columns in abi.PEER order
+    from dragonboat_amd import abi
+    last, committed = abi.PEER.names.index("last_index"), abi.PEER.names.index("committed")  # scalar fields first
+    assert np.all(state[:G, last] - state[:G, committed] == 2)  # a leader commits two passes behind
+    stats = np.load(tmp_path / "stats.npy")
+    assert stats[1] == 5 * 20000  # leader_commits over the timed passes
 
 
 def test_gpu_config3_read_index_quiesced(gpu):

@@ -20,13 +20,14 @@
 #   genclock          config 5 with GR_WAVE_CLOCK: the general kernel's wave phases
 #   wirepath          tools/bench_wire_path.py at 1M x 3, full and compact outboxes
 #   smoke             __graft_entry__.smoke()
-# Defaults: BENCH_ARGS="--steps 20 --warmup 5 --cpu-baseline off --host-path off".
+# Defaults: BENCH_ARGS="--full --steps 20 --warmup 5 --cpu-baseline off --host-path off"
+# (--full: the roofline block the bench step prints from).
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 OUT=gpurun_out
 mkdir -p $OUT
 R=$PWD
-: "${BENCH_ARGS:=--steps 20 --warmup 5 --cpu-baseline off --host-path off}"
+: "${BENCH_ARGS:=--full --steps 20 --warmup 5 --cpu-baseline off --host-path off}"
 : "${CFG_ARGS:=--passes 10}"
 : "${TESTS:=tests}"
 

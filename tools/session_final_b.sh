@@ -5,4 +5,4 @@ cd "${GRAFT_REPO_ROOT}" && mkdir -p gpurun_out || exit 1
 bash tools/gpu.sh warm "cfgprofile@r06_configs:PMC_ONLY=2+3+5" "configs@final:CFG_ARGS=--passes+10" || exit $?
 python tools/configs_summary.py gpurun_out/cfgprof_r06_configs gpurun_out/cfg_final.json > gpurun_out/configs_latest.json || exit 1
 cp gpurun_out/configs_latest.json profiles/configs_latest.json || exit 1
-bash tools/gpu.sh "bench@final:BENCH_ARGS=--steps+20+--warmup+5" || exit $?
+bash tools/gpu.sh "bench@final:BENCH_ARGS=--full+--steps+20+--warmup+5" || exit $?
