@@ -54,6 +54,15 @@ PEER = np.dtype([
     ("state", u8), ("n_runs", u8), ("self_slot", u8), ("flags", u8), ("read_index_count", u8),
     ("pad", u8, (3,)),
 ])
+# gr_peer with its vote tally bytes named (gpuraft.h votes_granted / votes_rejected:
+# a candidate's tally over remote slots, 0 unless state == CANDIDATE): the same
+# 664 bytes, so recs.view(PEER_VOTES) reads and writes them in place. PEER keeps
+# them inside "pad": bench.py --dump-outputs writes one column per named field of
+# PEER, and those columns are compared from one build to the next.
+PEER_VOTES = np.dtype([(n, PEER.fields[n][0]) for n in PEER.names if n != "pad"] +
+                      [("votes_granted", u8), ("votes_rejected", u8), ("pad", u8, (1,))])
+assert PEER_VOTES.itemsize == PEER.itemsize and \
+    PEER_VOTES.fields["votes_granted"][1] == PEER.fields["pad"][1]
 MESSAGE = np.dtype([
     ("peer", u32), ("type", u8), ("slot", u8), ("reject", u8), ("n_runs", u8),
     ("n_entries", u32), ("run2_offset", u32),
@@ -84,6 +93,8 @@ CLOCAL = np.dtype([("peer", u32), ("propose_entries", u32), ("ticks", np.uint16)
 CRESULT = np.dtype([("peer", u32), ("escalation", u8), ("propose_result", u8), ("flags", u8), ("save_count", u8),
                     ("aux", u32), ("commit_lag", u32), ("last_index", u64)])
 assert CMSG.itemsize == 24 and CLOCAL.itemsize == 24 and CRESULT.itemsize == 24
+PROMOTION = np.dtype([("peer", u32), ("pad", u32), ("term", u64), ("noop_index", u64)])
+assert PROMOTION.itemsize == 24
 UPDATE_COMMIT = np.dtype([("stable_log_to", u64), ("stable_log_term", u64), ("applied_to", u64)])
 SIZES = {"gr_peer": 664, "gr_message": 80, "gr_local_input": 48, "gr_peer_result": 168,
          "gr_remote": 32, "gr_read_status": 32}
@@ -170,6 +181,7 @@ EXPORTS = [
     "gr_collect_results", "gr_space_decode", "gr_space_encode", "gr_timing_begin", "gr_timing_end",
     "gr_bind_nodes", "gr_step_wire", "gr_step_wire_compact",
     "gr_graph_capture", "gr_graph_replay", "gr_graph_destroy",
+    "gr_set_elections", "gr_get_elections", "gr_promotions",
 ]
 
 

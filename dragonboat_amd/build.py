@@ -26,6 +26,7 @@ COVER_LIB = os.path.join(ROOT, "dragonboat_amd", "_build", "libgpuraft_cover.so"
 ORACLE_LIB = os.path.join(ROOT, "oracle", "_build", "liboracle.so")
 KAT_BIN = os.path.join(ROOT, "oracle", "_build", "kat_tests")
 HOSTLANE_LIB = os.path.join(ROOT, "tests", "_build", "libhostlane.so")
+HOSTLANE_ELECT_LIB = os.path.join(ROOT, "tests", "_build", "libhostlane_elect.so")
 WIRE_SRC = os.path.join(ROOT, "dragonboat_amd", "csrc", "gr_wire.hip")
 WIRE_DEPS = [WIRE_SRC, os.path.join(ROOT, "include", "gpuraft_wire.h"), os.path.join(ROOT, "include", "gpuraft.h"),
              os.path.join(CSRC, "gr_scan.h")]
@@ -205,19 +206,26 @@ def build_oracle(force=False):
     return ORACLE_LIB
 
 
-def build_hostlane(force=False):
-    os.makedirs(os.path.dirname(HOSTLANE_LIB), exist_ok=True)
+def build_hostlane(force=False, out=HOSTLANE_LIB, extra=()):
+    os.makedirs(os.path.dirname(out), exist_ok=True)
     src = os.path.join(ROOT, "tests", "native", "hostlane.hip")
     deps = ENGINE_DEPS + [src]
-    if not (force or _stale(HOSTLANE_LIB, deps)):
-        return HOSTLANE_LIB
-    with _locked(HOSTLANE_LIB):
-        if not (force or _stale(HOSTLANE_LIB, deps)):
-            return HOSTLANE_LIB
-        _run([HIPCC, "--cuda-host-only", "-O2", "-g", "-std=c++17", "-fPIC", "-shared", "-DGR_COVERAGE",
+    if not (force or _stale(out, deps)):
+        return out
+    with _locked(out):
+        if not (force or _stale(out, deps)):
+            return out
+        _run([HIPCC, "--cuda-host-only", "-O2", "-g", "-std=c++17", "-fPIC", "-shared", "-DGR_COVERAGE", *extra,
               "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "dragonboat_amd", "csrc"),
-              src, "-o", HOSTLANE_LIB])
-    return HOSTLANE_LIB
+              src, "-o", out])
+    return out
+
+
+def build_hostlane_elect(force=False):
+    """libhostlane_elect.so: the same host lane with elections compiled on
+    (-DGR_ELECTIONS_FORCE=1; its harness zeroes StepParams, so the run-time
+    switch cannot reach it), for tests/test_elections_hostlane.py."""
+    return build_hostlane(force, HOSTLANE_ELECT_LIB, ("-DGR_ELECTIONS_FORCE=1",))
 
 
 ORACLE_SAN_LIB = os.path.join(ROOT, "oracle", "_build", "liboracle_san.so")
@@ -301,8 +309,8 @@ def build_tools(force=False):
 
 def build_all(force=False):
     # independent targets side by side (each engine build also compiles its units in parallel)
-    with ThreadPoolExecutor(4) as ex:
-        fs = [ex.submit(f, force) for f in (build_engine, build_engine_cover, build_hostlane, build_wire)]
+    with ThreadPoolExecutor(5) as ex:
+        fs = [ex.submit(f, force) for f in (build_engine, build_engine_cover, build_hostlane, build_hostlane_elect, build_wire)]
         build_oracle(force)
         build_wire_oracle(force)
         build_tools(force)

@@ -54,10 +54,31 @@ constexpr uint32_t CV_ESC_FIRST = CV_ESC_TERM_WINDOW;
 // the coverage test requires every other id to be reached.
 constexpr uint32_t CV_BAD_FIRST = CV_BAD_COMMITTED_PAST_LAST;
 
+// The election handlers' ids (gr_lane.h with StepParams::elections): a second
+// table with its own counters and read-out, so the first table, which the
+// election-free workloads must reach in full, stays as it is.
+#define GR_COVER_ELECT_IDS(X)                                                                 \
+  X(CAMPAIGN) X(CAMPAIGN_TRANSFER) X(VOTE_GRANT) X(VOTE_REJECT) X(VOTE_DROPPED_CHECK_QUORUM)     \
+  X(VOTE_HIGHER_TERM) X(C_VOTE_RESP_WIN) X(C_VOTE_RESP_LOSE) X(C_VOTE_RESP_PENDING)              \
+  X(C_VOTE_RESP_OBSERVER) X(C_REPLICATE) X(C_HEARTBEAT) X(F_TIMEOUT_NOW) X(PROMOTE_UNCOMMITTED)
+#define GR_COVER_ENUM(n) CE_##n,
+enum CoverElectId : uint32_t { GR_COVER_ELECT_IDS(GR_COVER_ENUM) CE_N };
+#undef GR_COVER_ENUM
+
 #ifdef GR_COVERAGE
 // one array per code object (the kernels of each slot count are their own translation unit)
 static __device__ unsigned long long gr_cover_dev[CV_N];
 inline unsigned long long gr_cover_host[CV_N];
+static __device__ unsigned long long gr_cover_elect_dev[CE_N];
+inline unsigned long long gr_cover_elect_host[CE_N];
+__host__ __device__ static inline void cover_elect_hit(uint32_t id) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  atomicAdd(&gr_cover_elect_dev[id], 1ull);
+#else
+  gr_cover_elect_host[id]++;
+#endif
+}
+#define GR_COVER_E(id) ::gr::cover_elect_hit(::gr::CE_##id)
 __host__ __device__ static inline void cover_hit(uint32_t id) {
 #if defined(__HIP_DEVICE_COMPILE__)
   atomicAdd(&gr_cover_dev[id], 1ull);
@@ -70,6 +91,7 @@ __host__ __device__ static inline void cover_hit(uint32_t id) {
 #define GR_CHECK_INV(cond, id) ((cond) ? (void)0 : ::gr::cover_hit(::gr::CV_##id))
 #else
 #define GR_COVER(id) ((void)0)
+#define GR_COVER_E(id) ((void)0)
 #define GR_COVER_ESC(e) ((void)0)
 #define GR_CHECK_INV(cond, id) ((void)0)
 #endif

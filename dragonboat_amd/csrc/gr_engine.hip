@@ -34,6 +34,10 @@ extern template hipError_t cover_read<1>(uint64_t*);
 extern template hipError_t cover_read<3>(uint64_t*);
 extern template hipError_t cover_read<5>(uint64_t*);
 extern template hipError_t cover_read<8>(uint64_t*);
+extern template hipError_t cover_elect_read<1>(uint64_t*);
+extern template hipError_t cover_elect_read<3>(uint64_t*);
+extern template hipError_t cover_elect_read<5>(uint64_t*);
+extern template hipError_t cover_elect_read<8>(uint64_t*);
 #endif
 
 // tick_lanes: launch the tick kernel (some lane may carry ticks or a ReadIndex).
@@ -101,6 +105,10 @@ struct gr_engine {
   uint8_t bin_general = 1;  // StepParams::bin_general (GR_BIN_GENERAL=0 at gr_create: off, A/B runs)
   uint32_t* tail_hint = nullptr;  // StepParams::tail_hint: pinned, host-visible (GR_TAIL_HINT=0: off)
   uint8_t tail_mode = 0;          // StepParams::tail_mode (GR_TAIL_MODE at gr_create: tests, A/B runs)
+  uint8_t elections = 0;          // StepParams::elections (gr_set_elections; GR_ELECTIONS=1 at gr_create)
+  // the promotion list (gr_promotions): a 16-byte header (count, overflow flag)
+  // and max_peers gr_promotion records, one device allocation
+  uint8_t* promo = nullptr;
   std::string wclock_path;
 
   // gr_step buffers (gr_io.h), grown on demand and reused
@@ -208,6 +216,8 @@ struct PhaseClock {
     if (_e != hipSuccess) return GR_EDEVICE;   \
   } while (0)
 
+constexpr size_t kPromoHeader = 16;
+
 StepParams base_params(gr_engine* e) {
   StepParams kp;
   memset(&kp, 0, sizeof(kp));
@@ -221,6 +231,10 @@ StepParams base_params(gr_engine* e) {
   kp.tail_hint = e->tail_hint;
   kp.tail_mode = e->tail_mode;
   kp.tick_stage = e->tick_stage;
+  kp.elections = e->elections;
+  kp.promo_hdr = (uint32_t*)e->promo;
+  kp.promo = (gr_promotion*)(e->promo + kPromoHeader);
+  kp.promo_cap = e->cfg.max_peers;
   return kp;
 }
 
@@ -400,6 +414,7 @@ int gr_create(const gr_config* cfg, gr_engine** out) {
   if (const char* sb = getenv("GR_SMALL_BLOCKS")) e->small_blocks = (uint32_t)strtoul(sb, nullptr, 10);
   if (const char* bg = getenv("GR_BIN_GENERAL")) e->bin_general = bg[0] == '1';
   if (const char* tm = getenv("GR_TAIL_MODE")) e->tail_mode = (uint8_t)(strtoul(tm, nullptr, 10) & 3u);
+  if (const char* el = getenv("GR_ELECTIONS")) e->elections = el[0] == '1';
   if (const char* wc = getenv("GR_WAVE_CLOCK")) {
     // two regions: the general kernel's waves, then the tick kernel's (gr_kernels.h)
     if (hipMalloc((void**)&e->wclock, 2 * (size_t)kGeneralWaveSlots * kWaveClockWords * 8) == hipSuccess &&
@@ -413,6 +428,7 @@ int gr_create(const gr_config* cfg, gr_engine** out) {
       hipMalloc((void**)&e->tick_stage, (size_t)kTickLists * tick_cap(e->cap) * kTickStageWords * 8) != hipSuccess ||
       hipMalloc((void**)&e->counters, 2 * kCounters * kCounterStride * 4) != hipSuccess ||
       hipMalloc((void**)&e->route_base, 2 * GR_SMAX * GR_SMAX * 4) != hipSuccess ||
+      hipMalloc((void**)&e->promo, kPromoHeader + (size_t)cfg->max_peers * sizeof(gr_promotion)) != hipSuccess ||
       hipMalloc((void**)&e->hints, 2 * hint_stride(e->cap)) != hipSuccess) {
     if (ds) (void)hipFree(ds);
     if (dl) (void)hipFree(dl);
@@ -427,6 +443,7 @@ int gr_create(const gr_config* cfg, gr_engine** out) {
       hipMemset(e->stats, 0, (size_t)e->stats_rows * NSTAT * 8) != hipSuccess ||
       hipMemset(e->counters, 0, 2 * kCounters * kCounterStride * 4) != hipSuccess ||
       hipMemset(e->hints, 0, 2 * hint_stride(e->cap)) != hipSuccess ||
+      hipMemset(e->promo, 0, kPromoHeader) != hipSuccess ||
       hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess) {
     gr_destroy(e);
     return GR_EDEVICE;
@@ -453,6 +470,7 @@ void gr_destroy(gr_engine* e) {
   if (e->counters) (void)hipFree(e->counters);
   if (e->route_base) (void)hipFree(e->route_base);
   if (e->hints) (void)hipFree(e->hints);
+  if (e->promo) (void)hipFree(e->promo);
   if (e->tail_hint) (void)hipHostFree(e->tail_hint);
   if (e->wclock) {
     std::vector<uint64_t> h(2 * (size_t)kGeneralWaveSlots * kWaveClockWords);
@@ -1784,6 +1802,35 @@ int gr_collect_results(gr_engine* e, uint32_t first, gr_peer_result* out, size_t
   return GR_OK;
 }
 
+int gr_set_elections(gr_engine* e, int on) {
+  if (!e) return GR_EINVAL;
+  std::lock_guard<std::mutex> guard(e->mu);
+  GR_REFUSE_PENDING(e);
+  e->elections = on ? 1 : 0;
+  return GR_OK;
+}
+
+int gr_get_elections(const gr_engine* e) { return e ? (int)e->elections : GR_EINVAL; }
+
+int gr_promotions(gr_engine* e, gr_promotion* out, size_t cap, size_t* n) {
+  if (!e || !n || (cap && !out)) return GR_EINVAL;
+  *n = 0;
+  std::lock_guard<std::mutex> guard(e->mu);
+  GR_REFUSE_PENDING(e);
+  HIPCHK(hipDeviceSynchronize());  // passes may run on the caller's streams (gr_step_device, graph replays)
+  uint32_t hdr[2] = {0, 0};
+  HIPCHK(hipMemcpy(hdr, e->promo, sizeof(hdr), hipMemcpyDeviceToHost));
+  const size_t have = std::min<size_t>(hdr[0], e->cfg.max_peers);
+  if (have > cap) {  // nothing drained: the caller comes back with room
+    *n = have;
+    return GR_ECAPACITY;
+  }
+  if (have) HIPCHK(hipMemcpy(out, e->promo + kPromoHeader, have * sizeof(gr_promotion), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemset(e->promo, 0, 4));  // the count; the overflow flag stays
+  *n = have;
+  return hdr[1] ? GR_ECAPACITY : GR_OK;
+}
+
 #ifdef GR_COVERAGE
 // Coverage build only (libgpuraft_cover.so): per-branch hit counts (gr_cover.h).
 int gr_coverage_read(uint64_t* out, uint32_t n) {
@@ -1799,6 +1846,22 @@ int gr_coverage_read(uint64_t* out, uint32_t n) {
 const char* gr_coverage_names() {
 #define GR_COVER_NAME(x) #x ","
   return GR_COVER_IDS(GR_COVER_NAME);
+#undef GR_COVER_NAME
+}
+// The election handlers' table (gr_cover.h GR_COVER_ELECT_IDS), read the same way.
+int gr_coverage_elect_read(uint64_t* out, uint32_t n) {
+  if (!out || n < CE_N) return GR_EINVAL;
+  HIPCHK(hipDeviceSynchronize());
+  for (uint32_t k = 0; k < CE_N; ++k) out[k] = 0;
+  HIPCHK(cover_elect_read<1>(out));
+  HIPCHK(cover_elect_read<3>(out));
+  HIPCHK(cover_elect_read<5>(out));
+  HIPCHK(cover_elect_read<8>(out));
+  return (int)CE_N;
+}
+const char* gr_coverage_elect_names() {
+#define GR_COVER_NAME(x) #x ","
+  return GR_COVER_ELECT_IDS(GR_COVER_NAME);
 #undef GR_COVER_NAME
 }
 #endif

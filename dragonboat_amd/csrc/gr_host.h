@@ -143,13 +143,23 @@ __host__ __device__ inline void set_u64_row(gr_peer& g, uint32_t row, uint32_t S
   r -= GR_Q;
   g.read_index[r].ctx_high = v;
 }
-// u8 rows: rifrom[Q], riack[Q]
-__host__ __device__ inline uint8_t get_u8_row(const gr_peer& g, uint32_t row, uint32_t) {
+// u8 rows: rifrom[Q], riack[Q]. A candidate's first two ack rows hold its vote
+// tally instead (gr_layout.h Rows::B_VOTES_*): its own granted bit is ORed in on
+// load (campaign() always records it, raft.go:783), and its record's ack_bits
+// read back 0 (its FIFO is empty). g.state is set before the u8 rows are
+// (the header row is a u64 row).
+__host__ __device__ inline uint8_t get_u8_row(const gr_peer& g, uint32_t row, uint32_t S) {
   if (row < GR_Q) return g.read_index[row].from_slot;
+  if (g.state == GR_CANDIDATE && row < GR_Q + 2) {
+    if (row == GR_Q + 1) return g.votes_rejected;
+    return (uint8_t)(g.votes_granted | (g.self_slot < S ? 1u << g.self_slot : 0u));
+  }
   return g.read_index[row - GR_Q].ack_bits;
 }
 __host__ __device__ inline void set_u8_row(gr_peer& g, uint32_t row, uint32_t, uint8_t v) {
   if (row < GR_Q) g.read_index[row].from_slot = v;
+  else if (g.state == GR_CANDIDATE && row == GR_Q) g.votes_granted = v;
+  else if (g.state == GR_CANDIDATE && row == GR_Q + 1) g.votes_rejected = v;
   else g.read_index[row - GR_Q].ack_bits = v;
 }
 

@@ -1112,6 +1112,14 @@ hipError_t cover_read(uint64_t* out) {
     for (uint32_t k = 0; k < CV_N; ++k) out[k] += h[k];
   return e;
 }
+template <int S>
+hipError_t cover_elect_read(uint64_t* out) {
+  unsigned long long h[CE_N];
+  const hipError_t e = hipMemcpyFromSymbol(h, HIP_SYMBOL(gr_cover_elect_dev), sizeof(h), 0, hipMemcpyDeviceToHost);
+  if (e == hipSuccess)
+    for (uint32_t k = 0; k < CE_N; ++k) out[k] += h[k];
+  return e;
+}
 #endif
 
 }  // namespace gr
@@ -1124,7 +1132,9 @@ hipError_t cover_read(uint64_t* out) {
   GR_INSTANTIATE_COVER(SS)                                                                                    \
   }
 #ifdef GR_COVERAGE
-#define GR_INSTANTIATE_COVER(SS) template hipError_t cover_read<SS>(uint64_t*);
+#define GR_INSTANTIATE_COVER(SS)                       \
+  template hipError_t cover_read<SS>(uint64_t*); \
+  template hipError_t cover_elect_read<SS>(uint64_t*);
 #else
 #define GR_INSTANTIATE_COVER(SS)
 #endif

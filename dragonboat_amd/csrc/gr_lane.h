@@ -10,6 +10,8 @@
 // returns an escalation code; the kernel then re-runs the lane on its pristine
 // state up to the escalating item, so every item is applied either entirely on
 // the device or entirely by the host (one source of truth).
+// Elections (campaign, votes, promotion: the "elections" section below) run
+// here only with StepParams::elections set; off, they escalate.
 //
 // Function-level citations are to /root/reference/internal/raft/*.go.
 #pragma once
@@ -39,6 +41,8 @@ enum : uint32_t {
   G_RI = 1u << 9,     // ReadIndex FIFO
   G_EUB = 1u << 10,   // entry_size_ub
   G_INMEM = 1u << 11, // inMemory.markerIndex / savedTo (truncating merges only)
+  G_VOTE = 1u << 12,  // vote (canGrantVote: vote handlers only)
+  G_TALLY = 1u << 13, // a candidate's vote tally (candidate lanes only)
   G_TICK = G_ETICK | G_TICKS,
 };
 // dirty bits (store)
@@ -47,6 +51,7 @@ enum : uint32_t {
   D_LEADER = 1u << 4, D_LTT = 1u << 5, D_ETICK = 1u << 6, D_HTICK = 1u << 7,
   D_RETIMEOUT = 1u << 8, D_STATE = 1u << 9, D_FLAGS = 1u << 10, D_WIN = 1u << 11,
   D_REM = 1u << 12, D_SNAP = 1u << 13, D_RI = 1u << 14, D_INMEM = 1u << 15,
+  D_TALLY = 1u << 16,
 };
 
 GR_HD bool is_leader_message(uint32_t t) {  // raft.go:986-989
@@ -112,6 +117,9 @@ struct Lane {
   uint64_t eub = 0;
   // G_INMEM
   uint64_t imk = 0, isv = 0;  // inMemory.markerIndex, savedTo
+  // G_VOTE / G_TALLY (elections)
+  uint64_t vote = 0;
+  uint32_t vgrant = 0, vreject = 0;  // raft.votes: bit j = slot j's first response granted / rejected
 
   // outputs of this pass
   uint64_t tclk[3] = {0, 0, 0};  // GR_WAVE_CLOCK phase marks (device builds): loads, run, store done
@@ -123,6 +131,11 @@ struct Lane {
   uint32_t fwd_n = 0, fwd_entries = 0;  // forwarded Propose batches appended this pass
   uint64_t committed0 = 0;
   uint32_t msgs_in = 0, msgs_out = 0, entries_in = 0;
+  // elections: becomeLeader ran this pass (its gr_promotion record is appended
+  // once, after the run that stands: step()); the campaign in progress comes
+  // from TimeoutNow (raft.isLeaderTransferTarget, set for that campaign only)
+  bool promoted = false, transfer_target = false;
+  uint64_t promo_term = 0, promo_index = 0;
 
 
   // The general kernel's message prefetch (round 5, device builds, S <= 3): the
@@ -215,6 +228,11 @@ struct Lane {
       imk = s64(SR_MARKER);
       isv = s64(SR_SAVED_TO);
     }
+    if (miss & G_VOTE) vote = s64(SR_VOTE);
+    if (miss & G_TALLY) {
+      vgrant = s8(R::B_VOTES_GRANTED);
+      vreject = s8(R::B_VOTES_REJECTED);
+    }
     loaded |= miss;
   }
 
@@ -245,7 +263,7 @@ struct Lane {
       }
     }
     if (dirty & D_TERM) s64(SR_TERM) = term;
-    if (dirty & D_VOTE) s64(SR_VOTE) = 0;  // reset() on a term change is the only vote write here
+    if (dirty & D_VOTE) s64(SR_VOTE) = vote;  // every writer of D_VOTE sets vote (reset(), the vote handlers)
     if (dirty & D_COMMITTED) s64(SR_COMMITTED) = committed;
     if (dirty & D_HI) s64(SR_LAST_INDEX) = hi;
     if (dirty & D_LEADER) s64(SR_LEADER_ID) = leader_id;
@@ -292,6 +310,12 @@ struct Lane {
           s8(R::B_RIACK + q) = (uint8_t)(riack >> (8 * q));
         }
       }
+    }
+    // the tally rows are a candidate's (gr_layout.h): any other state's lane
+    // leaves them to the FIFO
+    if ((dirty & D_TALLY) && state == GR_CANDIDATE) {
+      s8(R::B_VOTES_GRANTED) = (uint8_t)vgrant;
+      s8(R::B_VOTES_REJECTED) = (uint8_t)vreject;
     }
     // one header word for the small fields; the run bits follow term, committed
     // and the window (gr_layout.h)
@@ -671,8 +695,13 @@ struct Lane {
     const uint64_t rand_value = kp.ln.u64(LR_RAND)[i];
     if (term != t) {
       term = t;
-      dirty |= D_TERM | D_VOTE;  // vote = NoLeader
+      vote = 0;  // NoLeader
+      loaded |= G_VOTE;
+      dirty |= D_TERM | D_VOTE;
     }
+    vgrant = 0;  // r.votes = make(map[uint64]bool)
+    vreject = 0;
+    loaded |= G_TALLY;
     leader_id = 0;
     loaded |= G_LID;
     etick = 0;
@@ -1186,6 +1215,166 @@ struct Lane {
     return 0;
   }
 
+  // ---------------------------------------------------------------- elections
+  // Everything here runs only with elections on (gr_set_elections): off, the
+  // callers escalate as they always did.
+  GR_HD bool elections() const { return GR_ELECTIONS_FORCE || kp.elections; }
+  // entryLog.lastTerm (logentry.go:133-139): the newest run's term; an empty log
+  // (lastIndex 0) has term 0. A log emptied by a snapshot (lastIndex =
+  // firstIndex-1 > 0 and no run) ends at the snapshot's term, which the device
+  // does not hold.
+  GR_HD int last_term(uint64_t* t) {
+    need(G_CORE | G_WIN);
+    if (nruns == 0) {
+      *t = 0;
+      return hi == 0 ? 0 : GR_ESC_TERM_WINDOW;
+    }
+    *t = last_run_term();
+    return 0;
+  }
+  // becomeLeader (raft.go:689-702) with appendEntries (:643-654) of the empty
+  // entry. The device log has no entry types, so getPendingConfigChangeCount
+  // (:903-917), which scans (committed, lastIndex] for config changes, is known
+  // to be 0 only when that range is empty: any other promotion goes to the host.
+  GR_HD int become_leader() {
+    need(G_CORE | G_LEAD | G_WIN | G_REM);
+    if (committed < hi) {
+      GR_COVER_E(PROMOTE_UNCOMMITTED);
+      return GR_ESC_UNSUPPORTED;
+    }
+    if (state == GR_FOLLOWER || state == GR_OBSERVER) return GR_ESC_PANIC;
+    if (self >= (uint32_t)S) return GR_ESC_UNSUPPORTED;  // no remote of its own to advance
+    state = GR_LEADER;
+    dirty |= D_STATE;
+    GR_TRY(reset(term));
+    leader_id = node_id;
+    if (nruns > 0 && last_run_term() > term) return GR_ESC_PANIC;  // checkEntriesToAppend
+    win_push(hi + 1, term);
+    hi += 1;
+    dirty |= D_HI | D_REM;
+    try_update(self, hi);
+    if (quorum() == 1) {
+      bool c;
+      GR_TRY(try_commit(&c));
+    }
+    promoted = true;
+    promo_term = term;
+    promo_index = hi;
+    return 0;
+  }
+  // campaign (raft.go:779-807) with becomeCandidate (:676-687). transfer: the
+  // campaign comes from TimeoutNow, whose RequestVotes carry Hint = nodeID.
+  GR_HD int campaign(bool transfer) {
+    need(G_CORE | G_LEAD | G_REM);
+    if (state == GR_LEADER || state == GR_OBSERVER) return GR_ESC_PANIC;
+    // isSingleNodeQuorum: becomeCandidate and becomeLeader in one item draw
+    // twice. A campaign after another reset() of this pass has no draw left
+    // either, and a peer without a slot of its own cannot tally its own vote.
+    if (quorum() == 1 || rand_used || self >= (uint32_t)S) return GR_ESC_ELECTION;
+    if (transfer) GR_COVER_E(CAMPAIGN_TRANSFER);
+    else GR_COVER_E(CAMPAIGN);
+    state = GR_CANDIDATE;
+    dirty |= D_STATE;
+    GR_TRY(reset(term + 1));
+    vote = node_id;
+    loaded |= G_VOTE;
+    vgrant = 1u << self;  // handleVoteResp(r.nodeID, false), :783
+    vreject = 0;
+    dirty |= D_VOTE | D_TALLY;
+    OutMsg m;
+    m.type = GR_REQUEST_VOTE;
+    m.log_index = hi;
+    GR_TRY(last_term(&m.log_term));
+    m.hint = transfer ? node_id : 0;
+#pragma unroll 1
+    for (uint32_t j = 0; j < (uint32_t)S; ++j)  // r.remotes: voters only
+      if (rkind(j) == GR_SLOT_VOTER && j != self) GR_TRY(emit(j, m));
+    return 0;
+  }
+  // handleNodeRequestVote (raft.go:1088-1107) with canGrantVote (:1063-1067) and
+  // entryLog.upToDate (logentry.go:345-357).
+  GR_HD int request_vote(const InMsg& m, uint32_t from) {
+    need(G_CORE | G_WIN | G_REM | G_VOTE);
+    if (rkind(from) == GR_SLOT_EMPTY) return GR_ESC_UNSUPPORTED;  // no node id to vote for or answer
+    const uint64_t fid = remote_id(from);
+    const bool can_grant = vote == 0 || vote == fid || m.term > term;
+    uint64_t lt;
+    GR_TRY(last_term(&lt));
+    const bool up_to_date = m.log_term > lt || (m.log_term == lt && m.log_index >= hi);
+    OutMsg r;
+    r.type = GR_REQUEST_VOTE_RESP;
+    if (can_grant && up_to_date) {
+      GR_COVER_E(VOTE_GRANT);
+      zero_etick();
+      vote = fid;
+      dirty |= D_VOTE;
+    } else {
+      GR_COVER_E(VOTE_REJECT);
+      r.flags = MFL_REJECT;
+    }
+    return emit(from, r);
+  }
+  // dropRequestVoteFromHighTermNode (raft.go:991-1009), for a RequestVote whose
+  // term is above this peer's.
+  GR_HD bool drop_high_term_vote(const InMsg& m, uint32_t from) {
+    if (!(flags & GR_F_CHECK_QUORUM)) return false;
+    if (m.hint == remote_id(from)) return false;  // a leader transfer's campaign
+    need(G_LID | G_TICK);
+    return leader_id != 0 && etick < etimeout;
+  }
+  // handleCandidateRequestVoteResp (raft.go:1449-1464) with handleVoteResp (:759-777).
+  GR_HD int candidate_vote_resp(const InMsg& m, uint32_t from) {
+    need(G_CORE | G_REM | G_TALLY);
+    if (rkind(from) == GR_SLOT_EMPTY) return 0;  // Peer.Handle drops a non-member's response (peer.go:199-209)
+    if (rkind(from) == GR_SLOT_OBSERVER) {
+      GR_COVER_E(C_VOTE_RESP_OBSERVER);
+      return 0;
+    }
+    const uint32_t bit = 1u << from;
+    if (!((vgrant | vreject) & bit)) {  // the first response of a node stands
+      if (m.flags & MFL_REJECT) vreject |= bit;
+      else vgrant |= bit;
+      dirty |= D_TALLY;
+    }
+    const int q = quorum();
+    if (popc8(vgrant) == q) {
+      GR_COVER_E(C_VOTE_RESP_WIN);
+      GR_TRY(become_leader());
+      return broadcast_replicate();
+    }
+    if (popc8(vreject) == q) {
+      GR_COVER_E(C_VOTE_RESP_LOSE);
+      return become_follower(term, 0);
+    }
+    GR_COVER_E(C_VOTE_RESP_PENDING);
+    return 0;
+  }
+  // handleHeartbeatMessage (raft.go:923-931)
+  GR_HD int handle_heartbeat(const InMsg& m, uint32_t from) {
+    if (m.commit > committed) {
+      if (m.commit > hi) return GR_ESC_PANIC;
+      committed = m.commit;
+      dirty |= D_COMMITTED;
+    }
+    OutMsg o;
+    o.type = GR_HEARTBEAT_RESP;
+    o.hint = m.hint;
+    o.hint_high = m.hint_high;
+    return emit(from, o);
+  }
+  // handleFollowerTimeoutNow (raft.go:1407-1417): the clock moved forward to the
+  // election timeout; the campaign of that tick carries the transfer hint.
+  GR_HD int follower_timeout_now() {
+    need(G_CORE | G_TICK);
+    GR_COVER_E(F_TIMEOUT_NOW);
+    etick = retimeout;
+    dirty |= D_ETICK;
+    transfer_target = true;
+    const int e = tick();
+    transfer_target = false;
+    return e;
+  }
+
   // ---------------------------------------------------------------- ticks (kernel step 4)
   GR_HD int handle_election() {  // handleNodeElection, raft.go:1073-1086
     need(G_CORE | G_LEAD);
@@ -1194,7 +1383,8 @@ struct Lane {
       GR_COVER(TICK_ELECTION_SKIPPED);
       return 0;
     }
-    return GR_ESC_ELECTION;
+    if (!elections()) return GR_ESC_ELECTION;
+    return campaign(transfer_target);
   }
   GR_HD int tick() {  // raft.go:377-429
     need(G_CORE | G_TICK);
@@ -1384,7 +1574,14 @@ struct Lane {
     const uint32_t t = m.type;
     if (m.term != 0 && m.term != term) {  // onMessageTermNotMatched
       if (m.term > term) {
-        if (t == GR_REQUEST_VOTE) return GR_ESC_UNSUPPORTED;  // dropRequestVoteFromHighTermNode + vote
+        if (t == GR_REQUEST_VOTE) {  // dropRequestVoteFromHighTermNode comes first (:1018)
+          if (!elections()) return GR_ESC_UNSUPPORTED;
+          if (drop_high_term_vote(m, from)) {
+            GR_COVER_E(VOTE_DROPPED_CHECK_QUORUM);
+            return 0;
+          }
+          GR_COVER_E(VOTE_HIGHER_TERM);
+        }
         const uint64_t lid = is_leader_message(t) ? remote_id(from) : 0;
         if (state == GR_OBSERVER) {
           GR_COVER(TERM_HIGHER_OBSERVER);
@@ -1448,7 +1645,7 @@ struct Lane {
         case GR_CHECK_QUORUM: GR_COVER(L_CHECK_QUORUM_MSG); return check_quorum();
         case GR_ELECTION: GR_COVER(L_ELECTION); return 0;
         case GR_PROPOSE: GR_COVER(L_PROPOSE_FWD); return leader_forwarded_propose(m);
-        case GR_REQUEST_VOTE: return GR_ESC_UNSUPPORTED;
+        case GR_REQUEST_VOTE: return elections() ? request_vote(m, from) : GR_ESC_UNSUPPORTED;
         default: GR_COVER(L_NIL); return 0;  // nil handler
       }
     }
@@ -1466,16 +1663,7 @@ struct Lane {
           else GR_COVER(F_HEARTBEAT);
           zero_etick();
           set_leader_from(from);
-          if (m.commit > committed) {
-            if (m.commit > hi) return GR_ESC_PANIC;
-            committed = m.commit;
-            dirty |= D_COMMITTED;
-          }
-          OutMsg o;
-          o.type = GR_HEARTBEAT_RESP;
-          o.hint = m.hint;
-          o.hint_high = m.hint_high;
-          return emit(from, o);
+          return handle_heartbeat(m, from);
         }
         case GR_READ_INDEX_RESP:  // raft.go:1391-1399
           if (obs) GR_COVER(O_READ_INDEX_RESP);
@@ -1509,19 +1697,34 @@ struct Lane {
         case GR_REQUEST_VOTE:
         case GR_TIMEOUT_NOW:
           if (obs) { GR_COVER(O_DROPPED); return 0; }
-          return GR_ESC_UNSUPPORTED;
+          if (!elections()) return GR_ESC_UNSUPPORTED;
+          return t == GR_REQUEST_VOTE ? request_vote(m, from) : follower_timeout_now();
         default: GR_COVER(F_NIL); return 0;
       }
     }
     switch (t) {  // candidate: every non-nil handler changes role or votes
       case GR_PROPOSE: GR_COVER(C_PROPOSE); return 0;  // handleCandidatePropose only logs
+      case GR_INSTALL_SNAPSHOT: return GR_ESC_UNSUPPORTED;
       case GR_HEARTBEAT:
       case GR_REPLICATE:
-      case GR_INSTALL_SNAPSHOT:
       case GR_REQUEST_VOTE_RESP:
       case GR_ELECTION:
-      case GR_REQUEST_VOTE: return GR_ESC_UNSUPPORTED;
+      case GR_REQUEST_VOTE: break;
       default: GR_COVER(C_NIL); return 0;
+    }
+    if (!elections()) return GR_ESC_UNSUPPORTED;
+    switch (t) {
+      case GR_HEARTBEAT:  // handleCandidateHeartbeat, raft.go:1444-1447
+        GR_COVER_E(C_HEARTBEAT);
+        GR_TRY(become_follower(term, remote_id(from)));
+        return handle_heartbeat(m, from);
+      case GR_REPLICATE:  // handleCandidateReplicate, raft.go:1433-1437
+        GR_COVER_E(C_REPLICATE);
+        GR_TRY(become_follower(term, remote_id(from)));
+        return handle_replicate(m, from);
+      case GR_REQUEST_VOTE_RESP: return candidate_vote_resp(m, from);
+      case GR_ELECTION: return handle_election();
+      default: return request_vote(m, from);
     }
   }
 
@@ -1602,6 +1805,27 @@ struct Lane {
     msgs_out = 0;
     entries_in = 0;
     outcnt = 0;
+    promoted = false;
+    transfer_target = false;
+  }
+  // This pass's promotion, for gr_promotions: one record, one returning atomic.
+  GR_HD void report_promotion() {
+    if (!kp.promo_hdr) return;
+#if defined(__HIP_DEVICE_COMPILE__)
+    const uint32_t x = atomicAdd(kp.promo_hdr, 1u);
+#else
+    const uint32_t x = kp.promo_hdr[0]++;
+#endif
+    if (x >= kp.promo_cap) {
+      kp.promo_hdr[1] = 1;  // sticky: the host reports GR_ECAPACITY
+      return;
+    }
+    gr_promotion r;
+    r.peer = p;
+    r.pad = 0;
+    r.term = promo_term;
+    r.noop_index = promo_index;
+    kp.promo[x] = r;
   }
   // Process items [0, limit); returns an escalation code and the item index
   // where it stopped (*at), or 0 with *at = number of items processed.
@@ -1700,6 +1924,7 @@ struct Lane {
       limit = at;
     }
     store();
+    if (promoted) report_promotion();  // of the run that stands (a re-run prefix included)
     tclk[2] = lane_clock(kp);
 #pragma unroll 1
     for (uint32_t j = 0; j < (uint32_t)S; ++j) {  // every routed mailbox is rewritten each pass

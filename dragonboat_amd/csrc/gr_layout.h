@@ -7,7 +7,8 @@
 // pointers (keeps the kernel argument small and in SGPRs).
 //   u64 rows: scalar fields, the header word, term-run window [GR_K] x2,
 //             remotes [S] x4, ReadIndex FIFO [GR_Q] x3
-//   u8 rows:  ReadIndex FIFO [GR_Q] x2 (requester slot, ack bitmap)
+//   u8 rows:  ReadIndex FIFO [GR_Q] x2 (requester slot, ack bitmap); a
+//             candidate's vote tally overlays the first two ack rows (Rows::B_VOTES_*)
 // The header word packs every small field a lane tests (state, self slot,
 // window run count, flags, FIFO count, and per remote slot state/active/kind):
 // one 8-byte load instead of 5 + 3S byte loads.
@@ -68,7 +69,16 @@ struct Rows {
   static constexpr uint32_t B_RIFROM = 0;             // + q
   static constexpr uint32_t B_RIACK = B_RIFROM + GR_Q;// + q
   static constexpr uint32_t NU8 = B_RIACK + GR_Q;
+  // A candidate's vote tally (raft.votes, raft.go:759-777): granted and
+  // rejected bitmaps over remote slots, overlaid on the FIFO's first two ack
+  // rows while state == GR_CANDIDATE. That FIFO is empty for every candidate
+  // (reset() clears it, raft.go:714, and no candidate handler adds to it), and
+  // nothing reads an ack row at or past the FIFO count, so the tally costs no
+  // row of its own and the tile stride stays what the steady state was tuned for.
+  static constexpr uint32_t B_VOTES_GRANTED = B_RIACK;
+  static constexpr uint32_t B_VOTES_REJECTED = B_RIACK + 1;
 };
+static_assert(GR_Q >= 2, "the vote tally overlays two ReadIndex ack rows");
 // Tile width of the tiled layouts (GR_TILE): 2^GR_TILE_SHIFT slots / positions.
 // 256 (a workgroup's four waves share each row segment: 2 KB per u64 row)
 // measured 0.1149 vs 0.1171 ms per 1M x 3 pass against 64, A/B in one call.
@@ -595,7 +605,21 @@ struct StepParams {
   // written by the steady kernel (nullptr: the tick lane loads everything itself)
   uint64_t* tick_stage;
   uint32_t pass_tag;  // the launch number: a record of this pass carries it
+  // elections on the device (gr_set_elections): wave-uniform, tested only where
+  // the general lane would otherwise escalate (gr_lane.h Lane::elections)
+  uint8_t elections;
+  // the promotion list (gr_promotions): promo_hdr[0] counts the records
+  // appended (one returning atomic per becomeLeader), promo_hdr[1] is set when
+  // one found the list full; nullptr: promotions leave no record (host builds)
+  uint32_t promo_cap;
+  uint32_t* promo_hdr;
+  gr_promotion* promo;
 };
+// -DGR_ELECTIONS_FORCE=1: elections on whatever StepParams::elections says (the
+// test-only host lane's second build, whose harness zeroes its StepParams).
+#ifndef GR_ELECTIONS_FORCE
+#define GR_ELECTIONS_FORCE 0
+#endif
 // A tick-list entry's staged inputs (round 5): the fields the steady kernel
 // loads for every lane of a wave that is not steady (coalesced: the wave's
 // quiesced lanes load the same lines), so the tick lane reads one 32-byte record

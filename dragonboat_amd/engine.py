@@ -118,6 +118,12 @@ def load_library(path=LIB_PATH):
     if hasattr(lib, "gr_coverage_read"):  # coverage build only (GR_COVERAGE)
         lib.gr_coverage_read.argtypes = [c.c_void_p, c.c_uint32]
         lib.gr_coverage_names.restype = c.c_char_p
+        lib.gr_coverage_elect_read.argtypes = [c.c_void_p, c.c_uint32]
+        lib.gr_coverage_elect_names.restype = c.c_char_p
+    if hasattr(lib, "gr_set_elections"):  # (older builds loaded for A/B runs lack elections)
+        lib.gr_set_elections.argtypes = [c.c_void_p, c.c_int]
+        lib.gr_get_elections.argtypes = [c.c_void_p]
+        lib.gr_promotions.argtypes = [c.c_void_p, c.c_void_p, c.c_size_t, c.POINTER(c.c_size_t)]
     if path == LIB_PATH:
         _lib = lib
     _libs[path] = lib
@@ -132,7 +138,10 @@ def _check(rc, what):
 class Engine:
     """One engine = one device's slab of group slots (engine slots 0..max_peers-1)."""
 
-    def __init__(self, max_peers, slots=3, device=0, max_entry_size=abi.MAX_ENTRY_SIZE, lib_path=None):
+    def __init__(self, max_peers, slots=3, device=0, max_entry_size=abi.MAX_ENTRY_SIZE, lib_path=None,
+                 elections=False):
+        """elections: run elections on the device (gr_set_elections); False leaves
+        the engine's default, which GR_ELECTIONS=1 in the environment turns on."""
         lib = load_library(lib_path or LIB_PATH)
         cfg = abi.Config(max_peers=max_peers, slots=slots, window_runs=abi.GR_K,
                          read_index_depth=abi.GR_Q, mailbox_depth=abi.GR_C, device=device,
@@ -143,6 +152,23 @@ class Engine:
         self.max_peers = max_peers
         self.slots = slots
         self.lib = lib
+        if elections:
+            self.set_elections(True)
+
+    def set_elections(self, on):
+        """Campaigns, votes and promotions on the device (gpuraft.h gr_set_elections)."""
+        _check(self.lib.gr_set_elections(self._h, 1 if on else 0), "gr_set_elections")
+
+    def get_elections(self):
+        return bool(self.lib.gr_get_elections(self._h))
+
+    def promotions(self):
+        """Drain the promotion list: abi.PROMOTION records (peer, term, noop_index)
+        of every peer that became leader on the device since the last call."""
+        out = np.zeros(self.max_peers, abi.PROMOTION)
+        n = ctypes.c_size_t()
+        _check(self.lib.gr_promotions(self._h, out.ctypes.data, len(out), ctypes.byref(n)), "gr_promotions")
+        return out[:n.value].copy()
 
     def close(self):
         if self._h:

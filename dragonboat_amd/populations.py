@@ -71,6 +71,28 @@ def make_groups(G, R=3, seed=2, term_lo=1, term_hi=5, base_index=2**32, spread=2
     return peers
 
 
+def cold_start(G, R=3, seed=2, election=10, check_quorum=False, **mk):
+    """Groups that lost their leader (a cold start, or a million groups whose
+    leader's host died): every replica a follower at its group's term with no
+    leader and no vote, logs equal and committed, election ticks and randomized
+    timeouts spread over [0, election) and [election, 2 * election)."""
+    peers = make_groups(G, R, seed=seed, election=election, check_quorum=check_quorum, **mk)
+    rng = np.random.default_rng(seed + 1000)
+    n = len(peers)
+    peers["state"] = abi.FOLLOWER
+    peers["leader_id"] = 0
+    peers["vote"] = 0
+    peers["election_tick"] = rng.integers(0, election, n)
+    peers["randomized_election_timeout"] = election + rng.integers(0, election, n)
+    for j in range(R):  # remotes as reset() leaves them
+        own = peers["self_slot"] == j
+        peers["remotes"][:, j]["match"] = np.where(own, peers["last_index"], 0)
+        peers["remotes"][:, j]["next"] = peers["last_index"] + np.uint64(1)
+        peers["remotes"][:, j]["state"] = abi.RETRY
+        peers["remotes"][:, j]["active"] = 0
+    return peers
+
+
 class Topology:
     """Replica-major topology: slot j of peer p talks to replica j of the same group."""
 

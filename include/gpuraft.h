@@ -72,8 +72,17 @@ enum gr_escalation {
   GR_ESC_NONE = 0,
   GR_ESC_TERM_WINDOW = 1,    /* term lookup below the device term window (LogReader.Term path) */
   GR_ESC_RANDOM = 2,         /* a second reset() in one pass needs another random draw */
-  GR_ESC_UNSUPPORTED = 3,    /* message/state pair handled by the host (votes, snapshots, candidate) */
-  GR_ESC_ELECTION = 4,       /* campaign() (raft.go:779-807) */
+  /* message/state pair handled by the host: snapshots; with elections off
+   * (gr_set_elections) also votes, TimeoutNow and every candidate handler; with
+   * elections on, a RequestVoteResp that would promote a candidate whose log
+   * has uncommitted entries (committed < last_index), and a RequestVote from a
+   * slot that is not a member */
+  GR_ESC_UNSUPPORTED = 3,
+  /* campaign() (raft.go:779-807): every campaign with elections off; with
+   * elections on, only the single-voter campaign (becomeCandidate and
+   * becomeLeader in one item need two draws), a campaign after the pass's draw
+   * was used, and a campaign by a peer that has no slot of its own */
+  GR_ESC_ELECTION = 4,
   GR_ESC_PANIC = 5,          /* the reference would panic on this item */
   GR_ESC_CAPACITY = 6,       /* mailbox / ReadIndex FIFO / ReadyToRead capacity */
   GR_ESC_SNAPSHOT = 7,       /* Replicate needs entries below firstIndex: InstallSnapshot path */
@@ -158,7 +167,15 @@ typedef struct gr_peer {
   uint8_t self_slot;       /* slot whose remote_id == node_id, GR_SLOT_NONE if self removed */
   uint8_t flags;           /* GR_F_* */
   uint8_t read_index_count;
-  uint8_t pad[3];
+  /* A candidate's vote tally (raft.votes, raft.go:759-777) as bitmaps over
+   * remote slots: bit j of votes_granted / votes_rejected is set when slot j's
+   * first RequestVoteResp granted / rejected. Meaningful only while state ==
+   * GR_CANDIDATE and exported as 0 otherwise. Loading a candidate ORs in its
+   * own granted bit (campaign() always records it, raft.go:783), so a record
+   * with both bytes 0 loads as a freshly campaigned candidate. */
+  uint8_t votes_granted;
+  uint8_t votes_rejected;
+  uint8_t pad[1];
 } gr_peer;
 
 /*
@@ -568,6 +585,36 @@ int gr_graph_replay(gr_graph* g, void* stream);
 void gr_graph_destroy(gr_graph* g);
 /* Copy per-peer results of the last device pass for peers [first, first+n). */
 int gr_collect_results(gr_engine* e, uint32_t first, gr_peer_result* out, size_t n);
+/* Elections on the device (off by default; GR_ELECTIONS=1 in the environment
+ * at gr_create turns them on). Off, every campaign, RequestVote, TimeoutNow and
+ * candidate handler escalates (GR_ESC_ELECTION / GR_ESC_UNSUPPORTED). On, the
+ * general lane runs campaign() (raft.go:779-807), handleNodeRequestVote
+ * (:1088-1107), handleCandidateRequestVoteResp (:1449-1464), becomeLeader
+ * (:689-702), the candidate's Replicate and Heartbeat handlers (:1433-1447) and
+ * handleFollowerTimeoutNow (:1407-1417); see gr_escalation for what still goes
+ * to the host. The switch applies to passes launched after the call; a captured
+ * graph keeps the setting it was captured with. gr_get_elections: 0 or 1
+ * (GR_EINVAL for a NULL engine). */
+int gr_set_elections(gr_engine* e, int on);
+int gr_get_elections(const gr_engine* e);
+/* becomeLeader appends an empty entry at the new term (raft.go:700) that no
+ * result field announces: every peer promoted on the device since the last
+ * call leaves one record here, and the host persists the empty entry
+ * {Index = noop_index, Term = term} with the pass's EntriesToSave. The call
+ * waits for the device, copies at most `cap` records to `out`, sets *n to the
+ * number copied and empties the list; order is unspecified. The list holds
+ * max_peers records: a promotion that finds it full is lost and every later call
+ * returns GR_ECAPACITY (records are still copied), as does a call whose `cap`
+ * is below the number pending (nothing is drained then; *n is the number
+ * pending). Works after gr_step, gr_step_compact, gr_step_device and graph
+ * replays. */
+typedef struct gr_promotion {
+  uint32_t peer; /* engine slot */
+  uint32_t pad;
+  uint64_t term;
+  uint64_t noop_index; /* last_index after the promotion's empty entry */
+} gr_promotion;
+int gr_promotions(gr_engine* e, gr_promotion* out, size_t cap, size_t* n);
 /* The wire path (SURVEY.md §8f-2 feeding the inbox): decoded raftpb.Message
  * records (gpuraft_wire.h grw_message / grw_entry, device pointers as
  * grw_decode_device leaves them in HBM) go straight into a gr_step pass, so the
