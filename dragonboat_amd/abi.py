@@ -95,6 +95,12 @@ CRESULT = np.dtype([("peer", u32), ("escalation", u8), ("propose_result", u8), (
 assert CMSG.itemsize == 24 and CLOCAL.itemsize == 24 and CRESULT.itemsize == 24
 PROMOTION = np.dtype([("peer", u32), ("pad", u32), ("term", u64), ("noop_index", u64)])
 assert PROMOTION.itemsize == 24
+# gr_quiesce_state: one peer's quiesceManager (quiesce.go:24-34). QUIESCE is
+# the message type above, so the record's dtype carries the struct's name.
+QUIESCE_STATE = np.dtype([("tick", u64), ("election_tick", u64), ("quiesced_since", u64),
+                          ("no_activity_since", u64),
+                          ("exit_quiesce_tick", u64), ("enabled", u8), ("pad", u8, (7,))])
+assert QUIESCE_STATE.itemsize == 48
 UPDATE_COMMIT = np.dtype([("stable_log_to", u64), ("stable_log_term", u64), ("applied_to", u64)])
 SIZES = {"gr_peer": 664, "gr_message": 80, "gr_local_input": 48, "gr_peer_result": 168,
          "gr_remote": 32, "gr_read_status": 32}
@@ -182,7 +188,19 @@ EXPORTS = [
     "gr_bind_nodes", "gr_step_wire", "gr_step_wire_compact",
     "gr_graph_capture", "gr_graph_replay", "gr_graph_destroy",
     "gr_set_elections", "gr_get_elections", "gr_promotions",
+    "gr_set_quiesce", "gr_get_quiesce", "gr_load_quiesce", "gr_sync_quiesce", "gr_load_quiesce_peers",
+    "gr_sync_quiesce_peers", "gr_tick_all", "gr_splitmix64",
 ]
+
+
+def splitmix64(x):
+    """gr_splitmix64 (gpuraft.h): gr_tick_all gives engine slot p the draw
+    splitmix64(rand_seed + p)."""
+    m = (1 << 64) - 1
+    x = (x + 0x9E3779B97F4A7C15) & m
+    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & m
+    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & m
+    return x ^ (x >> 31)
 
 
 def inbox_of(msgs, locals_):

@@ -18,7 +18,7 @@ CSRC = os.path.join(ROOT, "dragonboat_amd", "csrc")
 ENGINE_SRC = [os.path.join(CSRC, "gr_engine.hip")] + [os.path.join(CSRC, f"gr_kernels_s{s}.hip") for s in (1, 3, 5, 8)]
 ENGINE_DEPS = ENGINE_SRC + [os.path.join(CSRC, f)
                             for f in ("gr_lane.h", "gr_layout.h", "gr_host.h", "gr_fast.h", "gr_steady.h", "gr_tick.h", "gr_io.h",
-                                      "gr_cover.h", "gr_kernels.h", "gr_scan.h")] + \
+                                      "gr_cover.h", "gr_kernels.h", "gr_scan.h", "gr_quiesce.h")] + \
     [os.path.join(ROOT, "include", "gpuraft.h")]
 JOBS = max(1, min(8, os.cpu_count() or 1))
 ENGINE_LIB = os.path.join(ROOT, "dragonboat_amd", "_build", "libgpuraft.so")
@@ -27,6 +27,7 @@ ORACLE_LIB = os.path.join(ROOT, "oracle", "_build", "liboracle.so")
 KAT_BIN = os.path.join(ROOT, "oracle", "_build", "kat_tests")
 HOSTLANE_LIB = os.path.join(ROOT, "tests", "_build", "libhostlane.so")
 HOSTLANE_ELECT_LIB = os.path.join(ROOT, "tests", "_build", "libhostlane_elect.so")
+QUIESCE_HOST_LIB = os.path.join(ROOT, "tests", "_build", "libquiesce_host.so")
 WIRE_SRC = os.path.join(ROOT, "dragonboat_amd", "csrc", "gr_wire.hip")
 WIRE_DEPS = [WIRE_SRC, os.path.join(ROOT, "include", "gpuraft_wire.h"), os.path.join(ROOT, "include", "gpuraft.h"),
              os.path.join(CSRC, "gr_scan.h")]
@@ -228,6 +229,21 @@ def build_hostlane_elect(force=False):
     return build_hostlane(force, HOSTLANE_ELECT_LIB, ("-DGR_ELECTIONS_FORCE=1",))
 
 
+def build_quiesce_host(force=False):
+    """libquiesce_host.so: gr_quiesce.h (the quiesce manager the device kernel
+    runs) compiled by g++ behind a C interface, for tests/test_quiesce.py."""
+    os.makedirs(os.path.dirname(QUIESCE_HOST_LIB), exist_ok=True)
+    src = os.path.join(ROOT, "tests", "native", "quiesce_host.cpp")
+    deps = [src, os.path.join(CSRC, "gr_quiesce.h"), os.path.join(ROOT, "include", "gpuraft.h")]
+    if not (force or _stale(QUIESCE_HOST_LIB, deps)):
+        return QUIESCE_HOST_LIB
+    with _locked(QUIESCE_HOST_LIB):
+        if force or _stale(QUIESCE_HOST_LIB, deps):
+            _run(["g++", "-std=c++17", "-O2", "-g", "-fPIC", "-shared", "-I" + os.path.join(ROOT, "include"),
+                  "-I" + CSRC, src, "-o", QUIESCE_HOST_LIB])
+    return QUIESCE_HOST_LIB
+
+
 ORACLE_SAN_LIB = os.path.join(ROOT, "oracle", "_build", "liboracle_san.so")
 KAT_SAN_BIN = os.path.join(ROOT, "oracle", "_build", "kat_tests_san")
 HOSTLANE_SAN_LIB = os.path.join(ROOT, "tests", "_build", "libhostlane_san.so")
@@ -314,5 +330,6 @@ def build_all(force=False):
         build_oracle(force)
         build_wire_oracle(force)
         build_tools(force)
+        build_quiesce_host(force)
         for f in fs:
             f.result()

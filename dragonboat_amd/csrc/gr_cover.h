@@ -65,6 +65,16 @@ constexpr uint32_t CV_BAD_FIRST = CV_BAD_COMMITTED_PAST_LAST;
 enum CoverElectId : uint32_t { GR_COVER_ELECT_IDS(GR_COVER_ENUM) CE_N };
 #undef GR_COVER_ENUM
 
+// The quiesce pass's ids (gr_kernels.h gr_quiesce_kernel and the general lane's
+// sends and prefix re-run, with StepParams::quiesce): a third table, read out
+// through gr_coverage_quiesce_read, so the first two stay as they are.
+#define GR_COVER_QUIESCE_IDS(X)                                                               \
+  X(LANE) X(UNIFORM_MAILBOX) X(FULL_MAILBOX) X(NOTICE) X(HEARTBEAT_HINT) X(READ_INDEX) X(SPLIT)  \
+  X(MARK) X(SEND) X(PREFIX) X(PREFIX_SEND)
+#define GR_COVER_ENUM(n) CQ_##n,
+enum CoverQuiesceId : uint32_t { GR_COVER_QUIESCE_IDS(GR_COVER_ENUM) CQ_N };
+#undef GR_COVER_ENUM
+
 #ifdef GR_COVERAGE
 // one array per code object (the kernels of each slot count are their own translation unit)
 static __device__ unsigned long long gr_cover_dev[CV_N];
@@ -79,6 +89,16 @@ __host__ __device__ static inline void cover_elect_hit(uint32_t id) {
 #endif
 }
 #define GR_COVER_E(id) ::gr::cover_elect_hit(::gr::CE_##id)
+static __device__ unsigned long long gr_cover_quiesce_dev[CQ_N];
+inline unsigned long long gr_cover_quiesce_host[CQ_N];
+__host__ __device__ static inline void cover_quiesce_hit(uint32_t id) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  atomicAdd(&gr_cover_quiesce_dev[id], 1ull);
+#else
+  gr_cover_quiesce_host[id]++;
+#endif
+}
+#define GR_COVER_Q(id) ::gr::cover_quiesce_hit(::gr::CQ_##id)
 __host__ __device__ static inline void cover_hit(uint32_t id) {
 #if defined(__HIP_DEVICE_COMPILE__)
   atomicAdd(&gr_cover_dev[id], 1ull);
@@ -92,6 +112,7 @@ __host__ __device__ static inline void cover_hit(uint32_t id) {
 #else
 #define GR_COVER(id) ((void)0)
 #define GR_COVER_E(id) ((void)0)
+#define GR_COVER_Q(id) ((void)0)
 #define GR_COVER_ESC(e) ((void)0)
 #define GR_CHECK_INV(cond, id) ((void)0)
 #endif

@@ -38,6 +38,10 @@ extern template hipError_t cover_elect_read<1>(uint64_t*);
 extern template hipError_t cover_elect_read<3>(uint64_t*);
 extern template hipError_t cover_elect_read<5>(uint64_t*);
 extern template hipError_t cover_elect_read<8>(uint64_t*);
+extern template hipError_t cover_quiesce_read<1>(uint64_t*);
+extern template hipError_t cover_quiesce_read<3>(uint64_t*);
+extern template hipError_t cover_quiesce_read<5>(uint64_t*);
+extern template hipError_t cover_quiesce_read<8>(uint64_t*);
 #endif
 
 // tick_lanes: launch the tick kernel (some lane may carry ticks or a ReadIndex).
@@ -109,6 +113,16 @@ struct gr_engine {
   // the promotion list (gr_promotions): a 16-byte header (count, overflow flag)
   // and max_peers gr_promotion records, one device allocation
   uint8_t* promo = nullptr;
+  // the quiesce manager (gr_set_quiesce; GR_QUIESCE_ON_DEVICE=1 at gr_create):
+  // one allocation, made by the first gr_load_quiesce or when the switch first
+  // goes on, of cap records (qrec), as many pre-pass records (qprev), the words
+  // no pass writes (qcfg) and the bound raw LocalTick counts (qraw)
+  uint8_t quiesce = 0;
+  uint8_t* qmem = nullptr;
+  QuiesceRec* qrec = nullptr;
+  QuiesceRec* qprev = nullptr;
+  uint32_t* qcfg = nullptr;
+  uint32_t* qraw = nullptr;
   std::string wclock_path;
 
   // gr_step buffers (gr_io.h), grown on demand and reused
@@ -235,7 +249,32 @@ StepParams base_params(gr_engine* e) {
   kp.promo_hdr = (uint32_t*)e->promo;
   kp.promo = (gr_promotion*)(e->promo + kPromoHeader);
   kp.promo_cap = e->cfg.max_peers;
+  kp.quiesce = e->quiesce;
+  kp.qrec = e->qrec;
+  kp.qprev = e->qprev;
+  kp.qcfg = e->qcfg;
+  kp.qraw = e->qraw;
   return kp;
+}
+
+// The quiesce records' allocation (zeroed: every manager disabled).
+int ensure_quiesce(gr_engine* e) {
+  if (e->qmem) return GR_OK;
+  const size_t cap = e->cap, bytes = cap * (2 * sizeof(QuiesceRec) + 8);
+  if (hipMalloc((void**)&e->qmem, bytes) != hipSuccess) {
+    e->qmem = nullptr;
+    return GR_ENOMEM;
+  }
+  if (hipMemset(e->qmem, 0, bytes) != hipSuccess) {
+    (void)hipFree(e->qmem);
+    e->qmem = nullptr;
+    return GR_EDEVICE;
+  }
+  e->qrec = (QuiesceRec*)e->qmem;
+  e->qprev = e->qrec + cap;
+  e->qcfg = (uint32_t*)(e->qprev + cap);
+  e->qraw = e->qcfg + cap;
+  return GR_OK;
 }
 
 int grow_device(void** p, size_t* have, size_t want) {
@@ -415,6 +454,7 @@ int gr_create(const gr_config* cfg, gr_engine** out) {
   if (const char* bg = getenv("GR_BIN_GENERAL")) e->bin_general = bg[0] == '1';
   if (const char* tm = getenv("GR_TAIL_MODE")) e->tail_mode = (uint8_t)(strtoul(tm, nullptr, 10) & 3u);
   if (const char* el = getenv("GR_ELECTIONS")) e->elections = el[0] == '1';
+  const char* qd = getenv("GR_QUIESCE_ON_DEVICE");
   if (const char* wc = getenv("GR_WAVE_CLOCK")) {
     // two regions: the general kernel's waves, then the tick kernel's (gr_kernels.h)
     if (hipMalloc((void**)&e->wclock, 2 * (size_t)kGeneralWaveSlots * kWaveClockWords * 8) == hipSuccess &&
@@ -455,6 +495,14 @@ int gr_create(const gr_config* cfg, gr_engine** out) {
     else
       *(volatile uint32_t*)e->tail_hint = kTailAll;
   }
+  if (qd && qd[0] == '1') {
+    const int r = ensure_quiesce(e);
+    if (r) {
+      gr_destroy(e);
+      return r;
+    }
+    e->quiesce = 1;
+  }
   *out = e;
   return GR_OK;
 }
@@ -471,6 +519,7 @@ void gr_destroy(gr_engine* e) {
   if (e->route_base) (void)hipFree(e->route_base);
   if (e->hints) (void)hipFree(e->hints);
   if (e->promo) (void)hipFree(e->promo);
+  if (e->qmem) (void)hipFree(e->qmem);
   if (e->tail_hint) (void)hipHostFree(e->tail_hint);
   if (e->wclock) {
     std::vector<uint64_t> h(2 * (size_t)kGeneralWaveSlots * kWaveClockWords);
@@ -950,6 +999,10 @@ static int step_staged(gr_engine* e, uint32_t nm, const gr_local_input* locals, 
     HIPCHK(hipMemcpyAsync(e->d_locals.p, locals, (size_t)nlc * sizeof(gr_local_input), hipMemcpyHostToDevice, s));
   HIPCHK(hipMemsetAsync(mark, 0, (size_t)cap * 4, s));
   HIPCHK(hipMemsetAsync(scal, 0, 16, s));
+  if (e->quiesce && nlc) {  // ticks are LocalTicks: a QuiescedTick count is refused (scal[1], read below)
+    hipLaunchKernelGGL(io::check_raw_ticks, dim3(io_grid(nlc)), blk, 0, s, dloc, nlc, scal + 1);
+    HIPCHK(hipGetLastError());
+  }
   hipLaunchKernelGGL(io::mark_inputs, dim3(io_grid(nm + nlc)), blk, 0, s, dmsgs, nm, dloc, nlc, S, cap, mark,
                      scal + 1);
   HIPCHK(hipGetLastError());
@@ -1003,6 +1056,7 @@ static int step_staged(gr_engine* e, uint32_t nm, const gr_local_input* locals, 
   kp.in = vin;
   kp.out = vout;
   kp.n_lanes = nl;
+  kp.qraw = e->ln.u32(LR_TICKS);  // this pass's rows are the raw input: the quiesce pass rewrites them in place
   HIPCHK(launch_slots(S, kp, e->bail, e->counters, e->cap, (uint32_t)e->launches++, s, next_timing(e)));
   e->passes++;
   e->locals_set = false;    // the lane rows now hold this pass's compact locals
@@ -1312,6 +1366,10 @@ int gr_step_compact_begin(gr_engine* e, const gr_cinbox* in) {
     HIPCHK(hipMemcpyAsync(e->d_lext.p, in->ext_locals, (size_t)nlx * sizeof(gr_local_input), hipMemcpyHostToDevice, s));
   HIPCHK(hipMemsetAsync(mark, 0, (size_t)cap * 4, s));
   HIPCHK(hipMemsetAsync(scal, 0, 16, s));
+  if (e->quiesce && nlc + nlx) {  // as gr_step: no QuiescedTick counts with the manager on the device
+    hipLaunchKernelGGL(io::check_raw_ticks_c, dim3(io_grid(nlc + nlx)), blk, 0, s, ci.loc, nlc, ci.lext, nlx, scal + 1);
+    HIPCHK(hipGetLastError());
+  }
   hipLaunchKernelGGL(io::mark_inputs_c, dim3(io_grid(nm + nlc)), blk, 0, s, ci, S, cap, mark, scal + 1);
   HIPCHK(hipGetLastError());
   if ((r = io_scan(e, mark, lop, cap, s))) return r;
@@ -1407,6 +1465,7 @@ int gr_step_compact_end(gr_engine* e, gr_coutbox* out) {
   kp.in = vin;
   kp.out = vout;
   kp.n_lanes = nl;
+  kp.qraw = e->ln.u32(LR_TICKS);  // this pass's rows are the raw input: the quiesce pass rewrites them in place
   HIPCHK(launch_slots(S, kp, e->bail, e->counters, e->cap, (uint32_t)e->launches++, s, next_timing(e)));
   e->passes++;
   e->locals_set = false;
@@ -1637,6 +1696,9 @@ int gr_set_locals(gr_engine* e, const gr_local_input* locals, size_t n) {
     if (locals[k].peer >= cap) return GR_EINVAL;
   std::lock_guard<std::mutex> guard(e->mu);
   GR_REFUSE_PENDING(e);
+  if (e->quiesce)  // ticks are LocalTicks: the device decides the split (nothing is written)
+    for (size_t k = 0; k < n; ++k)
+      if (locals[k].quiesced_ticks) return GR_EINVAL;
   HIPCHK(hipDeviceSynchronize());  // a pass in flight on another stream may read the rows
   const hipStream_t s = e->stream;
   int r;
@@ -1653,6 +1715,8 @@ int gr_set_locals(gr_engine* e, const gr_local_input* locals, size_t n) {
   hipLaunchKernelGGL(io::fill_locals, dim3(io_grid(cap)), dim3(io::kIoBlock), 0, s, dloc,
                      (const uint32_t*)e->d_win.p, cap, e->ln);
   HIPCHK(hipGetLastError());
+  if (e->quiesce)  // the raw LocalTick counts, apart from the rows the quiesce pass rewrites
+    HIPCHK(hipMemcpyAsync(e->qraw, e->ln.u32(LR_TICKS), (size_t)cap * 4, hipMemcpyDeviceToDevice, s));
   HIPCHK(hipStreamSynchronize(s));
   e->locals_set = n > 0;
   bool other = false;
@@ -1671,7 +1735,8 @@ static int step_device_locked(gr_engine* e, const void* in_space, void* out_spac
                               uint32_t in_positions, uint32_t out_chunks, uint32_t out_positions, uint32_t depth,
                               uint32_t n_peers, void* stream) {
   StepParams kp = base_params(e);
-  kp.has_locals = e->locals_set ? 1 : 0;
+  kp.has_locals = e->locals_set || e->quiesce ? 1 : 0;  // the quiesce pass writes every lane's effective rows
+  kp.q_nolocals = e->locals_set ? 0 : 1;
   kp.has_lane_peer = 0;
   kp.route_mode = e->routes_bound ? e->route_mode : RT_IDENTITY;
   kp.route_g = e->route_g;
@@ -1812,6 +1877,114 @@ int gr_set_elections(gr_engine* e, int on) {
 
 int gr_get_elections(const gr_engine* e) { return e ? (int)e->elections : GR_EINVAL; }
 
+int gr_set_quiesce(gr_engine* e, int on) {
+  if (!e) return GR_EINVAL;
+  std::lock_guard<std::mutex> guard(e->mu);
+  GR_REFUSE_PENDING(e);
+  const uint8_t v = on ? 1 : 0;
+  if (v == e->quiesce) return GR_OK;
+  HIPCHK(hipDeviceSynchronize());
+  if (v) {
+    const int r = ensure_quiesce(e);
+    if (r) return r;
+  }
+  e->quiesce = v;
+  // bound locals mean LocalTicks on one side of the switch and a host-chosen
+  // split on the other: bind again
+  e->locals_set = false;
+  e->locals_other = false;
+  return GR_OK;
+}
+
+int gr_get_quiesce(const gr_engine* e) { return e ? (int)e->quiesce : GR_EINVAL; }
+
+// gr_quiesce_state records <-> the device records for slots [first, first+n) or a
+// slot list, as transfer() moves gr_peer records.
+static int transfer_quiesce(gr_engine* e, const uint32_t* slots, uint32_t first, size_t n, gr_quiesce_state* host,
+                            bool to_device) {
+  if (!e || (n && !host)) return GR_EINVAL;
+  const uint32_t cap = e->cfg.max_peers;
+  if (!slots && (uint64_t)first + n > cap) return GR_ERANGE;
+  if (n == 0) return GR_OK;
+  if (n >= 0x80000000ull) return GR_EINVAL;
+  std::lock_guard<std::mutex> guard(e->mu);
+  GR_REFUSE_PENDING(e);
+  HIPCHK(hipDeviceSynchronize());  // passes in flight on other streams own the records
+  const hipStream_t s = e->stream;
+  const size_t bytes = n * sizeof(gr_quiesce_state);
+  int r;
+  if ((r = ensure_quiesce(e))) return r;
+  if ((r = grow_device(&e->d_peers.p, &e->d_peers.n, bytes))) return r;
+  if ((r = grow_device(&e->d_mark.p, &e->d_mark.n, (size_t)cap * 4))) return r;
+  if ((r = grow_device(&e->d_scal.p, &e->d_scal.n, 16))) return r;
+  if ((r = grow_pinned(&e->h_scal, &e->h_scal_bytes, 16))) return r;
+  const uint32_t* dslots = nullptr;
+  if (slots) {
+    if ((r = grow_device(&e->d_slots.p, &e->d_slots.n, n * 4))) return r;
+    HIPCHK(hipMemcpyAsync(e->d_slots.p, slots, n * 4, hipMemcpyHostToDevice, s));
+    dslots = (const uint32_t*)e->d_slots.p;
+  }
+  gr_quiesce_state* dq = (gr_quiesce_state*)e->d_peers.p;
+  const dim3 grid(io_grid(n)), blk(io::kIoBlock);
+  if (to_device) HIPCHK(hipMemcpyAsync(dq, host, bytes, hipMemcpyHostToDevice, s));
+  if (to_device || slots) {  // nothing is written (or read back) when a record or the list is refused
+    if (slots) HIPCHK(hipMemsetAsync(e->d_mark.p, 0, (size_t)cap * 4, s));
+    HIPCHK(hipMemsetAsync(e->d_scal.p, 0, 16, s));
+    hipLaunchKernelGGL(io::check_quiesce, grid, blk, 0, s, to_device ? (const gr_quiesce_state*)dq : nullptr, dslots,
+                       (uint32_t)n, cap, (uint32_t*)e->d_mark.p, (uint32_t*)e->d_scal.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(e->h_scal, e->d_scal.p, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    const uint32_t err = *(uint32_t*)e->h_scal;
+    if (err & 2u) return GR_ERANGE;
+    if (err & 1u) return GR_EINVAL;
+  }
+  if (to_device) {
+    hipLaunchKernelGGL(io::quiesce_to_rows, grid, blk, 0, s, (const gr_quiesce_state*)dq, dslots, first, (uint32_t)n,
+                       e->qrec, e->qcfg);
+    HIPCHK(hipGetLastError());
+  } else {
+    hipLaunchKernelGGL(io::rows_to_quiesce, grid, blk, 0, s, (const QuiesceRec*)e->qrec, (const uint32_t*)e->qcfg,
+                       dslots, first, (uint32_t)n, dq);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(host, dq, bytes, hipMemcpyDeviceToHost, s));
+  }
+  HIPCHK(hipStreamSynchronize(s));
+  return GR_OK;
+}
+
+int gr_load_quiesce(gr_engine* e, uint32_t first, const gr_quiesce_state* recs, size_t n) {
+  return transfer_quiesce(e, nullptr, first, n, const_cast<gr_quiesce_state*>(recs), true);
+}
+int gr_sync_quiesce(gr_engine* e, uint32_t first, gr_quiesce_state* out, size_t n) {
+  return transfer_quiesce(e, nullptr, first, n, out, false);
+}
+int gr_load_quiesce_peers(gr_engine* e, const uint32_t* slots, const gr_quiesce_state* recs, size_t n) {
+  if (n && !slots) return GR_EINVAL;
+  return transfer_quiesce(e, slots, 0, n, const_cast<gr_quiesce_state*>(recs), true);
+}
+int gr_sync_quiesce_peers(gr_engine* e, const uint32_t* slots, gr_quiesce_state* out, size_t n) {
+  if (n && !slots) return GR_EINVAL;
+  return transfer_quiesce(e, slots, 0, n, out, false);
+}
+
+int gr_tick_all(gr_engine* e, uint32_t ticks, uint64_t rand_seed) {
+  if (!e) return GR_EINVAL;
+  std::lock_guard<std::mutex> guard(e->mu);
+  GR_REFUSE_PENDING(e);
+  HIPCHK(hipDeviceSynchronize());  // a pass in flight on another stream may read the rows
+  const uint32_t cap = e->cfg.max_peers;
+  hipLaunchKernelGGL(io::fill_tick_all, dim3(io_grid(cap)), dim3(io::kIoBlock), 0, e->stream, cap, ticks, rand_seed,
+                     e->st, e->ln, e->qraw);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(e->stream));
+  e->locals_set = true;
+  e->locals_other = ticks != 0;
+  return GR_OK;
+}
+
+uint64_t gr_splitmix64(uint64_t x) { return q_splitmix64(x); }
+
 int gr_promotions(gr_engine* e, gr_promotion* out, size_t cap, size_t* n) {
   if (!e || !n || (cap && !out)) return GR_EINVAL;
   *n = 0;
@@ -1862,6 +2035,22 @@ int gr_coverage_elect_read(uint64_t* out, uint32_t n) {
 const char* gr_coverage_elect_names() {
 #define GR_COVER_NAME(x) #x ","
   return GR_COVER_ELECT_IDS(GR_COVER_NAME);
+#undef GR_COVER_NAME
+}
+// The quiesce pass's table (gr_cover.h GR_COVER_QUIESCE_IDS), read the same way.
+int gr_coverage_quiesce_read(uint64_t* out, uint32_t n) {
+  if (!out || n < CQ_N) return GR_EINVAL;
+  HIPCHK(hipDeviceSynchronize());
+  for (uint32_t k = 0; k < CQ_N; ++k) out[k] = 0;
+  HIPCHK(cover_quiesce_read<1>(out));
+  HIPCHK(cover_quiesce_read<3>(out));
+  HIPCHK(cover_quiesce_read<5>(out));
+  HIPCHK(cover_quiesce_read<8>(out));
+  return (int)CQ_N;
+}
+const char* gr_coverage_quiesce_names() {
+#define GR_COVER_NAME(x) #x ","
+  return GR_COVER_QUIESCE_IDS(GR_COVER_NAME);
 #undef GR_COVER_NAME
 }
 #endif

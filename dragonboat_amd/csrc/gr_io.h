@@ -166,6 +166,57 @@ __global__ void fill_locals(const gr_local_input* loc, const uint32_t* win, uint
   }
 }
 
+// ---- the quiesce manager's boundary (gr_quiesce.h; gpuraft.h gr_*_quiesce)
+// With the manager on the device a local record's ticks are LocalTicks and its
+// quiesced_ticks must be 0: *err is set before anything of the pass runs.
+__global__ void check_raw_ticks(const gr_local_input* loc, uint32_t n, uint32_t* err) {
+  for (uint32_t k = io_tid(); k < n; k += io_stride())
+    if (loc[k].quiesced_ticks) atomicOr(err, 1u);
+}
+__global__ void check_raw_ticks_c(const gr_clocal* loc, uint32_t n, const gr_local_input* lext, uint32_t n_lext,
+                                  uint32_t* err) {
+  for (uint32_t k = io_tid(); k < n + n_lext; k += io_stride())
+    if (k < n ? loc[k].quiesced_ticks != 0 : lext[k - n].quiesced_ticks != 0) atomicOr(err, 1u);
+}
+// Slot x of a load: in range, listed once, and a record the device encoding holds.
+__global__ void check_quiesce(const gr_quiesce_state* in, const uint32_t* slots, uint32_t n, uint32_t cap,
+                              uint32_t* mark, uint32_t* err) {
+  for (uint32_t x = io_tid(); x < n; x += io_stride()) {
+    if (in && !q_encodable(in[x])) atomicOr(err, 1u);  // ERR_PEER
+    if (slots && (slots[x] >= cap || atomicAdd(mark + slots[x], 1u) != 0)) atomicOr(err, 2u);  // ERR_SLOT
+  }
+}
+__global__ void quiesce_to_rows(const gr_quiesce_state* in, const uint32_t* slots, uint32_t first, uint32_t n,
+                                QuiesceRec* rec, uint32_t* cfg) {
+  for (uint32_t x = io_tid(); x < n; x += io_stride()) {
+    const uint32_t p = slots ? slots[x] : first + x;
+    rec[p] = q_encode(q_from_state(in[x]));
+    cfg[p] = q_cfg(in[x]);
+  }
+}
+__global__ void rows_to_quiesce(const QuiesceRec* rec, const uint32_t* cfg, const uint32_t* slots, uint32_t first,
+                                uint32_t n, gr_quiesce_state* out) {
+  for (uint32_t x = io_tid(); x < n; x += io_stride()) {
+    const uint32_t p = slots ? slots[x] : first + x;
+    out[x] = q_to_state(q_decode(rec[p], cfg[p]));
+  }
+}
+// gr_tick_all: `ticks` LocalTicks and nothing else for every slot that holds a
+// group (a loaded group has an election timeout; raft cannot tick without one),
+// the draw splitmix64(seed + slot); every other slot gets an empty input. raw:
+// the quiesce pass's LocalTick counts (nullptr before the records exist).
+__global__ void fill_tick_all(uint32_t cap, uint32_t ticks, uint64_t seed, StateBase st, LaneBase L, uint32_t* raw) {
+  for (uint32_t p = io_tid(); p < cap; p += io_stride()) {
+    gr_local_input x{};
+    x.peer = p;
+    x.ticks = st.u64(SR_ETIMEOUT)[p] ? ticks : 0u;
+    x.rand = q_splitmix64(seed + p);
+    host::locals_to_rows(x, L.u32(LR_TICKS) + p, L.u32(LR_QTICKS) + p, L.u32(LR_PROPOSE) + p, L.u8(LR_LFLAGS) + p,
+                         L.u64(LR_RI_LO) + p, L.u64(LR_RI_HI) + p, L.u64(LR_RAND) + p, L.u32(LR_LWORD) + p);
+    if (raw) raw[p] = x.ticks;
+  }
+}
+
 // Messages each lane emitted (RT_IDENTITY out space, mailbox j*nl + lane).
 __global__ void out_counts(SpaceView out, uint32_t nl, uint32_t S, uint32_t* oc) {
   for (uint32_t l = io_tid(); l < nl; l += io_stride()) {

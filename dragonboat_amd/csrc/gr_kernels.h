@@ -884,6 +884,120 @@ __global__ __launch_bounds__(kBlock, 1) void gr_small_kernel(StepParams kp, uint
   if (kp.stats) block_stats(kp, ls);
 }
 
+// Pass 0, with StepParams::quiesce: the quiesce manager (gr_quiesce.h) for every
+// lane, ahead of the step kernels. One lane per peer: it reads the peer's
+// record, its raw local input (LocalTick count, ReadIndex flag) and its
+// in-mailbox count bytes in one round of loads; a uniform mailbox's types follow
+// from the count byte, only a wave with a full-record mailbox reads tags and the
+// heartbeats' Hint from the cold records (a second round, every load issued
+// before the first is used). It writes the new record, the pre-pass record of a
+// peer with input (qprev: the general lane re-runs the manager over an escalated
+// lane's prefix from it), and the effective LR_TICKS, LR_QTICKS and LR_LWORD the
+// step kernels read; LW_QSEND marks a lane whose manager entered quiesce. The
+// raw counts live apart (qraw), so bound locals and graphs replay.
+template <int S>
+__global__ __launch_bounds__(kBlock) void gr_quiesce_kernel(StepParams kp) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  const bool active = i < kp.n_lanes;
+  const uint32_t li = active ? i : 0u;  // idle lanes of the last wave shadow lane 0 and store nothing
+  const uint32_t p = kp.has_lane_peer ? kp.ln.u32(LR_LANE_PEER)[li] : li;
+  uint32_t gin[S], gout[S];
+  routes_of<S>(kp, li, gin, gout);
+  // ---- round 1
+  const QuiesceRec old = kp.qrec[p];
+  const uint32_t cfg = kp.qcfg[p];
+  const bool loc = !kp.q_nolocals;
+  const uint32_t raw = loc ? kp.qraw[li] : 0u;
+  const uint32_t lf = loc ? (uint32_t)kp.ln.u8(LR_LFLAGS)[li] : 0u;
+  const uint32_t np = loc ? kp.ln.u32(LR_PROPOSE)[li] : 0u;
+  uint32_t cbs[S], cnt[S];
+#pragma unroll
+  for (int j = 0; j < S; ++j) {
+    const uint32_t c = kp.in.at(gin[j] != NOPOS ? gin[j] : 0u).cnt();
+    cbs[j] = gin[j] != NOPOS ? c : 0u;
+  }
+  uint32_t nmsg = 0;
+  bool anyfull = false;
+#pragma unroll
+  for (int j = 0; j < S; ++j) {
+    const uint32_t n = mb_n(cbs[j]);
+    cnt[j] = n < kp.in.depth ? n : kp.in.depth;  // an overflowed mailbox escalates at message `depth`
+    nmsg += cnt[j];
+    anyfull = anyfull || (cnt[j] && !(cbs[j] & MB_UNIFORM));
+  }
+  // ---- round 2 (waves with a full-record mailbox): tag and Hint of every message
+  uint32_t tag[S][GR_C];
+  bool hnz[S][GR_C];
+#pragma unroll
+  for (int j = 0; j < S; ++j) {
+#pragma unroll
+    for (int k = 0; k < GR_C; ++k) {
+      tag[j][k] = 0;
+      hnz[j][k] = false;
+    }
+  }
+  if (__any(active && anyfull)) {
+    uint64_t hv[S][GR_C];
+#pragma unroll
+    for (int j = 0; j < S; ++j) {
+#pragma unroll
+      for (int k = 0; k < GR_C; ++k) {
+        const bool has = (uint32_t)k < cnt[j] && !(cbs[j] & MB_UNIFORM);
+        const Mailbox mb = kp.in.at(has ? gin[j] : 0u);
+        const uint32_t kk = has ? (uint32_t)k : 0u;
+        tag[j][k] = mb.tag(kk);
+        hv[j][k] = mb.u64(kk, MF_HINT);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < S; ++j) {
+#pragma unroll
+      for (int k = 0; k < GR_C; ++k) {
+        tag[j][k] = keep_value(tag[j][k]);
+        hnz[j][k] = keep_value(hv[j][k]) != 0;
+      }
+    }
+  }
+  QuiesceMgr q = q_decode(old, cfg);
+  const bool ri = (lf & LF_READ_INDEX) != 0;
+  const QuiescePass r = q_run_pass(q, ri, nmsg, raw, 0xFFFFFFFFu, [&](uint32_t, auto sink) {
+#pragma unroll
+    for (int j = 0; j < S; ++j) {
+      const bool uni = (cbs[j] & MB_UNIFORM) != 0;
+      if (cnt[j]) {
+        if (uni) GR_COVER_Q(UNIFORM_MAILBOX);
+        else GR_COVER_Q(FULL_MAILBOX);
+      }
+#pragma unroll
+      for (int k = 0; k < GR_C; ++k) {
+        if ((uint32_t)k < cnt[j]) {
+          const uint32_t t = uni ? ((cbs[j] & MB_RESP) ? (uint32_t)GR_REPLICATE_RESP : (uint32_t)GR_REPLICATE)
+                                 : (tag[j][k] & 0xFFu);
+          if (t == GR_QUIESCE) GR_COVER_Q(NOTICE);
+          if ((t == GR_HEARTBEAT || t == GR_HEARTBEAT_RESP) && hnz[j][k]) GR_COVER_Q(HEARTBEAT_HINT);
+          sink(t, !uni && hnz[j][k]);
+        }
+      }
+    }
+  });
+  if (!active) return;
+  if (nmsg || raw || ri) {
+    GR_COVER_Q(LANE);
+    if (ri) GR_COVER_Q(READ_INDEX);
+    if (r.ticks && r.quiesced_ticks) GR_COVER_Q(SPLIT);
+    if (r.send) GR_COVER_Q(MARK);
+    kp.qprev[p] = old;
+    kp.qrec[p] = q_encode(q);
+  }
+  kp.ln.u32(LR_TICKS)[i] = r.ticks;
+  kp.ln.u32(LR_QTICKS)[i] = r.quiesced_ticks;
+  kp.ln.u32(LR_LWORD)[i] = r.send ? (LW_OTHER | LW_QSEND) : local_word(r.ticks, r.quiesced_ticks, np, lf);
+  if (!loc) {  // nothing bound: the step kernels read these rows all the same
+    kp.ln.u8(LR_LFLAGS)[i] = 0;
+    kp.ln.u32(LR_PROPOSE)[i] = 0;
+  }
+}
+
 // Optional per-pass timing: events around the two kernels, recorded on the
 // pass's stream.
 struct PassTiming {
@@ -1051,6 +1165,11 @@ hipError_t launch(const StepParams& kp_in, uint32_t* bail_list, uint32_t* counte
   uint32_t* nxt = counters + ((parity + 1) & 1) * kCounters * kCounterStride;
   hipError_t err;
   if (t && (err = hipEventRecord(t->ev[0], s)) != hipSuccess) return err;
+  if (kp.quiesce) {  // the manager decides this pass's Tick / QuiescedTick split first (timed with the lean kernels)
+    hipLaunchKernelGGL(gr_quiesce_kernel<S>, dim3(blocks), dim3(kBlock), 0, s, kp);
+    if ((err = hipGetLastError()) != hipSuccess) return err;
+    tick_lanes = true;  // the split is the device's: plan as for ticks
+  }
   if (blocks <= kp.small_blocks) {  // the whole pass in one launch
     hipLaunchKernelGGL(gr_small_kernel<S>, dim3(blocks), dim3(kBlock), 0, s, kp, nxt);
     if ((err = hipGetLastError()) != hipSuccess) return err;
@@ -1120,6 +1239,14 @@ hipError_t cover_elect_read(uint64_t* out) {
     for (uint32_t k = 0; k < CE_N; ++k) out[k] += h[k];
   return e;
 }
+template <int S>
+hipError_t cover_quiesce_read(uint64_t* out) {
+  unsigned long long h[CQ_N];
+  const hipError_t e = hipMemcpyFromSymbol(h, HIP_SYMBOL(gr_cover_quiesce_dev), sizeof(h), 0, hipMemcpyDeviceToHost);
+  if (e == hipSuccess)
+    for (uint32_t k = 0; k < CQ_N; ++k) out[k] += h[k];
+  return e;
+}
 #endif
 
 }  // namespace gr
@@ -1134,7 +1261,8 @@ hipError_t cover_elect_read(uint64_t* out) {
 #ifdef GR_COVERAGE
 #define GR_INSTANTIATE_COVER(SS)                       \
   template hipError_t cover_read<SS>(uint64_t*); \
-  template hipError_t cover_elect_read<SS>(uint64_t*);
+  template hipError_t cover_elect_read<SS>(uint64_t*); \
+  template hipError_t cover_quiesce_read<SS>(uint64_t*);
 #else
 #define GR_INSTANTIATE_COVER(SS)
 #endif

@@ -544,6 +544,7 @@ struct Lane {
 #endif
   uint32_t gin_[S], gout_[S], pcb_[S];
   uint32_t plf_ = 0, pnt_ = 0, pnq_ = 0, pnp_ = 0;
+  uint32_t plw_ = 0;  // with StepParams::quiesce: the effective locals word (its LW_QSEND mark)
   GR_HD void preload() {
     if (!GR_LANE_PRELOAD) return;
 #pragma unroll
@@ -558,6 +559,7 @@ struct Lane {
       pnt_ = kp.ln.u32(LR_TICKS)[i];
       pnq_ = kp.ln.u32(LR_QTICKS)[i];
       pnp_ = kp.ln.u32(LR_PROPOSE)[i];
+      if (kp.quiesce) plw_ = kp.ln.u32(LR_LWORD)[i];
     }
   }
   // Issue the message prefetch (pf_): every piece of every (slot, message) pair
@@ -601,7 +603,8 @@ struct Lane {
     if (g == NOPOS) return GR_ESC_NONMEMBER;
     const uint32_t c = (outcnt >> (3 * j)) & 7u;
     if (c >= kp.out.depth) return GR_ESC_CAPACITY;
-    const uint64_t mterm = is_request_message(m.type) ? m.term : term;
+    // a Quiesce message is the node's, not raft's (node.go:530-543): Term stays 0
+    const uint64_t mterm = is_request_message(m.type) || m.type == GR_QUIESCE ? m.term : term;
     if (wide_term(mterm, m.log_term, m.rt0, m.rt1)) return GR_ESC_WIDE_TERM;
     const Mailbox mb = kp.out.at(g);
     mb.type(c) = m.type;
@@ -1827,6 +1830,56 @@ struct Lane {
     r.noop_index = promo_index;
     kp.promo[x] = r;
   }
+  // sendEnterQuiesceMessages (node.go:530-543): one Quiesce message to every
+  // voter but this node (observers get none), sent by stepNode before getUpdate
+  // (node.go:643-646), so ahead of everything else the pass emits.
+  GR_HD int send_quiesce() {
+    need(G_CORE | G_REM);
+    GR_COVER_Q(SEND);
+    OutMsg o;
+    o.type = GR_QUIESCE;
+#pragma unroll 1
+    for (uint32_t j = 0; j < (uint32_t)S; ++j)
+      if (rkind(j) == GR_SLOT_VOTER && j != self) GR_TRY(emit(j, o));
+    return 0;
+  }
+  // The quiesce manager over the items below `limit` of an escalated lane, from
+  // the pre-pass record gr_quiesce_kernel kept (the in space is still intact):
+  // the record then reflects exactly the prefix the host is told was applied.
+  // Returns whether the manager entered quiesce inside the prefix.
+  GR_HD bool quiesce_prefix(uint32_t limit) {
+    const uint32_t lf = GR_LANE_PRELOAD ? plf_ : kp.ln.u8(LR_LFLAGS)[i];
+    const uint32_t raw = GR_LANE_PRELOAD ? pnt_ + pnq_ : kp.ln.u32(LR_TICKS)[i] + kp.ln.u32(LR_QTICKS)[i];
+    const bool ri = (lf & LF_READ_INDEX) != 0;
+    uint32_t nmsg = 0;
+#pragma unroll 1
+    for (uint32_t j = 0; j < (uint32_t)S; ++j) {
+      const uint32_t g = in_gpos(j);
+      if (g == NOPOS) continue;
+      const uint32_t n = mb_n(GR_LANE_PRELOAD ? sel(pcb_, j) : (uint32_t)kp.in.at(g).cnt());
+      nmsg += n < kp.in.depth ? n : kp.in.depth;
+    }
+    if (!nmsg && !raw && !ri) return false;  // no item of the manager's: the kernel left the record alone
+    GR_COVER_Q(PREFIX);
+    QuiesceMgr q = q_decode(kp.qprev[p], kp.qcfg[p]);
+    const QuiescePass r = q_run_pass(q, ri, nmsg, raw, limit, [&](uint32_t nm, auto sink) {
+      uint32_t x = 0;
+#pragma unroll 1
+      for (uint32_t j = 0; j < (uint32_t)S && x < nm; ++j) {
+        const uint32_t g = in_gpos(j);
+        if (g == NOPOS) continue;
+        const Mailbox mb = kp.in.at(g);
+        const uint32_t cb = GR_LANE_PRELOAD ? sel(pcb_, j) : (uint32_t)mb.cnt();
+        const uint32_t n = mb_n(cb), c = n < kp.in.depth ? n : kp.in.depth;
+#pragma unroll 1
+        for (uint32_t k = 0; k < c && x < nm; ++k, ++x)
+          sink(mb.tag_at(k, cb) & 0xFFu, !(cb & MB_UNIFORM) && mb.u64(k, MF_HINT) != 0);
+      }
+    });
+    kp.qrec[p] = q_encode(q);
+    if (r.send) GR_COVER_Q(PREFIX_SEND);
+    return r.send;
+  }
   // Process items [0, limit); returns an escalation code and the item index
   // where it stopped (*at), or 0 with *at = number of items processed.
   GR_HD int run(uint32_t limit, uint32_t* at) {
@@ -1910,6 +1963,8 @@ struct Lane {
     int esc = 0;
     preload();
     prefetch();
+    bool qsend = kp.quiesce && kp.has_locals &&
+                 ((GR_LANE_PRELOAD ? plw_ : kp.ln.u32(LR_LWORD)[i]) & LW_QSEND) != 0;
 #pragma unroll 1
     for (int attempt = 0; attempt < 2; ++attempt) {  // one call site keeps run() inlined
       begin();
@@ -1917,11 +1972,17 @@ struct Lane {
       // instead of one dependent round per group as the handlers reach them
       need(G_CORE | G_WIN | G_REM | G_ETICK | G_LID);
       if (attempt == 0) tclk[0] = lane_clock(kp);
-      const int e = run(limit, &at);
+      int e = 0;
+      if (qsend) {  // the Quiesce messages come first; one that finds no place escalates at item 0
+        at = 0;
+        e = send_quiesce();
+      }
+      if (!e) e = run(limit, &at);
       if (attempt == 0) tclk[1] = lane_clock(kp);
       if (!e) break;
       esc = e;  // second attempt re-runs the prefix and cannot escalate
       limit = at;
+      if (kp.quiesce) qsend = quiesce_prefix(limit);  // ... and sends only if the entry lies below esc_item
     }
     store();
     if (promoted) report_promotion();  // of the run that stands (a re-run prefix included)

@@ -40,6 +40,7 @@
 #include <stdint.h>
 
 #include "gpuraft.h"
+#include "gr_quiesce.h"
 
 namespace gr {
 
@@ -273,6 +274,10 @@ constexpr uint8_t LF_PROPOSE_CC = 0x02;
 constexpr uint32_t LW_OTHER = 0x10000u;
 constexpr uint32_t LW_QT_SHIFT = 17, LW_QT_MAX = 0xFFu;
 constexpr uint32_t LW_TICK_SHIFT = 17, LW_TICK_MAX = 0xFFu, LW_RI = 1u << 25, LW_TICKONLY = 1u << 26;
+// The quiesce pass's send mark (gr_kernels.h gr_quiesce_kernel, always with
+// LW_OTHER and without LW_TICKONLY): the peer's manager entered quiesce this
+// pass, so the general lane steps the lane and sends its Quiesce messages first.
+constexpr uint32_t LW_QSEND = 1u << 27;
 __host__ __device__ inline uint32_t local_word(uint32_t ticks, uint32_t qticks, uint32_t propose, uint32_t lflags) {
   const bool other = ticks || lflags || propose > 0xFFFFu || qticks > LW_QT_MAX;
   if (!other) return propose | (qticks << LW_QT_SHIFT);
@@ -614,6 +619,18 @@ struct StepParams {
   uint32_t promo_cap;
   uint32_t* promo_hdr;
   gr_promotion* promo;
+  // the quiesce manager on the device (gr_set_quiesce; gr_quiesce.h): every pass
+  // starts with gr_quiesce_kernel, which reads the raw LocalTick counts (qraw,
+  // by lane), advances the records (qrec, by engine slot; qcfg is the part no
+  // pass writes), keeps each stepped peer's pre-pass record (qprev) for the
+  // general lane's prefix re-run and writes the effective LR_TICKS, LR_QTICKS
+  // and LR_LWORD. q_nolocals: no local input is bound (every raw input is 0).
+  uint8_t quiesce;
+  uint8_t q_nolocals;
+  QuiesceRec* qrec;
+  QuiesceRec* qprev;
+  const uint32_t* qcfg;
+  const uint32_t* qraw;
 };
 // -DGR_ELECTIONS_FORCE=1: elections on whatever StepParams::elections says (the
 // test-only host lane's second build, whose harness zeroes its StepParams).

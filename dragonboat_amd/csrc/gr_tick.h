@@ -278,6 +278,7 @@ struct TickLane {
     }
     const bool leader = state == GR_LEADER;
     GT_BAIL(!leader && state != GR_FOLLOWER);
+    GT_BAIL(lw & LW_QSEND);  // the peer announces its quiesce (gr_quiesce.h): the general lane sends
 #pragma unroll
     for (int j = 0; j < S; ++j)  // cold fields lost in the exchange (gr_io.h side_pack): general lane
       GT_BAIL(cnt[j] && !(cbs[j] & MB_UNIFORM) && (cbs[j] & MB_COLD_LOST));

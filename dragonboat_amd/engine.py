@@ -120,10 +120,23 @@ def load_library(path=LIB_PATH):
         lib.gr_coverage_names.restype = c.c_char_p
         lib.gr_coverage_elect_read.argtypes = [c.c_void_p, c.c_uint32]
         lib.gr_coverage_elect_names.restype = c.c_char_p
+    if hasattr(lib, "gr_coverage_quiesce_read"):
+        lib.gr_coverage_quiesce_read.argtypes = [c.c_void_p, c.c_uint32]
+        lib.gr_coverage_quiesce_names.restype = c.c_char_p
     if hasattr(lib, "gr_set_elections"):  # (older builds loaded for A/B runs lack elections)
         lib.gr_set_elections.argtypes = [c.c_void_p, c.c_int]
         lib.gr_get_elections.argtypes = [c.c_void_p]
         lib.gr_promotions.argtypes = [c.c_void_p, c.c_void_p, c.c_size_t, c.POINTER(c.c_size_t)]
+    if hasattr(lib, "gr_set_quiesce"):  # (older builds loaded for A/B runs lack the quiesce manager)
+        lib.gr_set_quiesce.argtypes = [c.c_void_p, c.c_int]
+        lib.gr_get_quiesce.argtypes = [c.c_void_p]
+        lib.gr_load_quiesce.argtypes = [c.c_void_p, c.c_uint32, c.c_void_p, c.c_size_t]
+        lib.gr_sync_quiesce.argtypes = [c.c_void_p, c.c_uint32, c.c_void_p, c.c_size_t]
+        lib.gr_load_quiesce_peers.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t]
+        lib.gr_sync_quiesce_peers.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t]
+        lib.gr_tick_all.argtypes = [c.c_void_p, c.c_uint32, c.c_uint64]
+        lib.gr_splitmix64.argtypes = [c.c_uint64]
+        lib.gr_splitmix64.restype = c.c_uint64
     if path == LIB_PATH:
         _lib = lib
     _libs[path] = lib
@@ -139,9 +152,11 @@ class Engine:
     """One engine = one device's slab of group slots (engine slots 0..max_peers-1)."""
 
     def __init__(self, max_peers, slots=3, device=0, max_entry_size=abi.MAX_ENTRY_SIZE, lib_path=None,
-                 elections=False):
+                 elections=False, quiesce=False):
         """elections: run elections on the device (gr_set_elections); False leaves
-        the engine's default, which GR_ELECTIONS=1 in the environment turns on."""
+        the engine's default, which GR_ELECTIONS=1 in the environment turns on.
+        quiesce: run the quiesce manager on the device (gr_set_quiesce); False
+        leaves the default, which GR_QUIESCE_ON_DEVICE=1 turns on."""
         lib = load_library(lib_path or LIB_PATH)
         cfg = abi.Config(max_peers=max_peers, slots=slots, window_runs=abi.GR_K,
                          read_index_depth=abi.GR_Q, mailbox_depth=abi.GR_C, device=device,
@@ -154,6 +169,8 @@ class Engine:
         self.lib = lib
         if elections:
             self.set_elections(True)
+        if quiesce:
+            self.set_quiesce(True)
 
     def set_elections(self, on):
         """Campaigns, votes and promotions on the device (gpuraft.h gr_set_elections)."""
@@ -161,6 +178,48 @@ class Engine:
 
     def get_elections(self):
         return bool(self.lib.gr_get_elections(self._h))
+
+    def set_quiesce(self, on):
+        """The quiesce manager on the device (gpuraft.h gr_set_quiesce): local
+        inputs then carry LocalTick counts and the device splits them. Drops
+        bound local inputs."""
+        _check(self.lib.gr_set_quiesce(self._h, 1 if on else 0), "gr_set_quiesce")
+
+    def get_quiesce(self):
+        return bool(self.lib.gr_get_quiesce(self._h))
+
+    def load_quiesce(self, recs, first=0, slots=None):
+        """abi.QUIESCE_STATE records into slots [first, first+n), or into a slot
+        list (gr_load_quiesce / gr_load_quiesce_peers)."""
+        recs = np.ascontiguousarray(recs, abi.QUIESCE_STATE)
+        ptr = recs.ctypes.data if len(recs) else None
+        if slots is None:
+            _check(self.lib.gr_load_quiesce(self._h, first, ptr, len(recs)), "gr_load_quiesce")
+            return
+        slots = np.ascontiguousarray(slots, np.uint32)
+        assert len(slots) == len(recs)
+        _check(self.lib.gr_load_quiesce_peers(self._h, slots.ctypes.data if len(slots) else None, ptr, len(recs)),
+               "gr_load_quiesce_peers")
+
+    def sync_quiesce(self, n=None, first=0, slots=None):
+        """The managers' records (gr_sync_quiesce / gr_sync_quiesce_peers)."""
+        if slots is None:
+            n = self.max_peers - first if n is None else n
+            out = np.zeros(n, abi.QUIESCE_STATE)
+            _check(self.lib.gr_sync_quiesce(self._h, first, out.ctypes.data if n else None, n), "gr_sync_quiesce")
+            return out
+        slots = np.ascontiguousarray(slots, np.uint32)
+        out = np.zeros(len(slots), abi.QUIESCE_STATE)
+        _check(self.lib.gr_sync_quiesce_peers(self._h, slots.ctypes.data if len(slots) else None,
+                                              out.ctypes.data if len(out) else None, len(slots)),
+               "gr_sync_quiesce_peers")
+        return out
+
+    def tick_all(self, ticks=1, rand_seed=0):
+        """gr_tick_all: bind `ticks` LocalTicks for every loaded slot of the
+        device-resident path, built on the device; slot p's draw is
+        abi.splitmix64(rand_seed + p)."""
+        _check(self.lib.gr_tick_all(self._h, ticks, rand_seed & ((1 << 64) - 1)), "gr_tick_all")
 
     def promotions(self):
         """Drain the promotion list: abi.PROMOTION records (peer, term, noop_index)

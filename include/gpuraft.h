@@ -615,6 +615,78 @@ typedef struct gr_promotion {
   uint64_t noop_index; /* last_index after the promotion's empty entry */
 } gr_promotion;
 int gr_promotions(gr_engine* e, gr_promotion* out, size_t cap, size_t* n);
+/*
+ * The quiesce manager on the device (off by default; GR_QUIESCE_ON_DEVICE=1 in
+ * the environment at gr_create turns it on). In the reference every node owns a
+ * quiesceManager (quiesce.go:24-125) that node.tick and node.handleReceivedMessages
+ * drive (node.go:687-693, 736-769, 782-786, 877-890): it decides which LocalTicks
+ * are Peer.Tick() and which Peer.QuiescedTick(), and when the node tells its
+ * voters that it went idle (node.go:530-543, 643-645). gr_quiesce_state is that
+ * manager's record, one per engine slot, kept in an allocation of its own; a
+ * slot never loaded is disabled (all zero). gr_load_* / gr_sync_* of a group
+ * leave it alone.
+ *
+ * With the switch on, every pass (gr_step, gr_step_compact, gr_step_wire,
+ * gr_step_device, graph replays) starts with one more kernel that runs the
+ * manager for every peer with input, in the reference's order: a local
+ * read_index is recordActivity(ReadIndex) before any message; then the messages
+ * by slot and arrival (Quiesce: tryEnterQuiesce; SnapshotStatus, Unreachable:
+ * nothing; a Heartbeat or HeartbeatResp with Hint > 0: recordActivity(ReadIndex);
+ * any other type: recordActivity(type)); then gr_local_input.ticks LocalTicks,
+ * each increaseQuiesceTick() followed by QuiescedTick when quiesced, else Tick.
+ * gr_local_input.ticks is then the LocalTick count and quiesced_ticks must be 0
+ * (GR_EINVAL before anything is written otherwise). A peer whose manager entered
+ * quiesce during the pass sends one GR_QUIESCE message (Term 0) to every voter
+ * slot but its own, ahead of everything else it sends to that slot in the pass;
+ * it takes a mailbox place like any message (GR_ESC_CAPACITY when there is none).
+ * For an escalated peer the record and the Quiesce messages reflect exactly the
+ * items below esc_item. A local ReadIndex counts as an item after the messages
+ * (as everywhere in this header), although its recordActivity runs first: it is
+ * below esc_item only when every message is. Two things stay with the host: a
+ * proposal's config-change flag records no activity here (the item escalates and
+ * the host re-runs it), and the `Replicate && busy` filter (node.go:758-760).
+ *
+ * The device keeps tick, quiesced_since, no_activity_since and
+ * exit_quiesce_tick in 32 bits and election_tick in 31: gr_load_quiesce refuses
+ * (GR_EINVAL, before anything is written) a record with a larger value or with
+ * enabled above 1. gr_sync_quiesce returns the fields exactly; a tick counter
+ * that reaches 2^32 on the device wraps, so reload before (13 years at 100 ms).
+ *
+ * Off, the records are kept but never read or written, and every result,
+ * record and escalation is what it was without this section. The switch applies
+ * to passes launched after the call; a captured graph keeps the setting it was
+ * captured with. Changing the switch drops the local inputs bound by
+ * gr_set_locals / gr_tick_all (their tick counts mean something else on the
+ * other side): bind again. gr_get_quiesce: 0 or 1 (GR_EINVAL for a NULL engine).
+ * Per-pass timing (gr_timing) counts the quiesce kernel with the lean kernels
+ * (fast_ms).
+ */
+typedef struct gr_quiesce_state {
+  uint64_t tick, election_tick, quiesced_since, no_activity_since, exit_quiesce_tick;
+  uint8_t enabled;
+  uint8_t pad[7];
+} gr_quiesce_state;
+int gr_set_quiesce(gr_engine* e, int on);
+int gr_get_quiesce(const gr_engine* e);
+/* Records of engine slots [first, first+n), or of a slot list (each listed once;
+ * GR_ERANGE for a slot out of range or listed twice, before anything is
+ * written, as gr_load_peers). */
+int gr_load_quiesce(gr_engine* e, uint32_t first, const gr_quiesce_state* recs, size_t n);
+int gr_sync_quiesce(gr_engine* e, uint32_t first, gr_quiesce_state* out, size_t n);
+int gr_load_quiesce_peers(gr_engine* e, const uint32_t* slots, const gr_quiesce_state* recs, size_t n);
+int gr_sync_quiesce_peers(gr_engine* e, const uint32_t* slots, gr_quiesce_state* out, size_t n);
+/* The broadcast tick of the device-resident path: binds, as gr_set_locals does
+ * but built by a device fill with no upload, `ticks` LocalTicks (and nothing
+ * else) for every engine slot that holds a group (a non-zero election_timeout:
+ * raft cannot tick without one); every other slot gets an empty input. Slot p's
+ * gr_local_input.rand is
+ * gr_splitmix64(rand_seed + p):
+ *   x += 0x9E3779B97F4A7C15; x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9;
+ *   x = (x ^ (x >> 27)) * 0x94D049BB133111EB; return x ^ (x >> 31);
+ * (all mod 2^64). With the quiesce switch off the ticks are Peer.Tick() calls,
+ * as gr_local_input.ticks always is then. */
+int gr_tick_all(gr_engine* e, uint32_t ticks, uint64_t rand_seed);
+uint64_t gr_splitmix64(uint64_t x);
 /* The wire path (SURVEY.md §8f-2 feeding the inbox): decoded raftpb.Message
  * records (gpuraft_wire.h grw_message / grw_entry, device pointers as
  * grw_decode_device leaves them in HBM) go straight into a gr_step pass, so the
