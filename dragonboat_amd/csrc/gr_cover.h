@@ -127,7 +127,8 @@ __host__ __device__ static inline void cover_hit(uint32_t id) {
 #ifdef GR_COVERAGE
 template <class StateBaseT>
 __host__ __device__ inline void check_state(const StateBaseT& st, uint32_t p) {
-  const uint64_t last = st.u64(SR_LAST_INDEX)[p], committed = st.u64(SR_COMMITTED)[p];
+  const uint64_t last = st.u64(SR_LAST_INDEX)[p];
+  const uint64_t committed = h_committed(st.u64(SR_HDR)[p], last, st.u64(SR_COMMITTED)[p]);  // H_CL
   GR_CHECK_INV(committed <= last, BAD_COMMITTED_PAST_LAST);
   const uint64_t h = st.u64(SR_HDR)[p];
   uint32_t nr = h_nruns(h);

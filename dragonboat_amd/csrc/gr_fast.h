@@ -450,6 +450,7 @@ struct FastLane {
     const bool gelo = h_gelo(hdr);
     const uint32_t flags = h_flags(hdr);
     lslot_out = (flags & F_LSLOT) >> F_LSLOT_SHIFT;
+    committed = h_committed(hdr, hi, committed);  // the lag field (gr_layout.h H_CL): the row may be stale
     cload = committed;
     if (nruns) {
       if (hruns && kRuns && (hdr & H_RUN_MASK) == H_RUN_MASK) {
@@ -745,9 +746,12 @@ struct FastLane {
     }
     if (!ok) return false;
     // ---- stores (nothing above this line has written state)
-    if (committed != committed0) ntst(s64(SR_COMMITTED), (uint64_t)(committed));
+    // committed: a final lag that fits goes into the header's lag field (H_CL) and
+    // the row is skipped; otherwise the row is written and the field cleared
+    const uint32_t cl = cl_of(hi, committed);
+    if (!cl && (h_cl(hdr) || committed != committed0)) ntst(s64(SR_COMMITTED), (uint64_t)(committed));
     if (hi != hi0) ntst(s64(SR_LAST_INDEX), (uint64_t)(hi));
-    uint64_t nh = hdr;  // the header word, rewritten once if anything in it changed
+    uint64_t nh = h_with_cl(hdr, cl);  // the header word, rewritten once if anything in it changed
     if (pushed) {
       // right-aligned window: the old newest run moves one row down, the new one
       // takes the last row; it starts above the old newest run, so H_GE_LO holds

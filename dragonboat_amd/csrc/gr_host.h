@@ -41,6 +41,8 @@ __host__ __device__ inline uint64_t header_of(const gr_peer& g, uint32_t S) {
     }
     if (g.self_slot < S && g.remotes[g.self_slot].match == g.last_index) h |= 1ull << H_MS_BIT;
   }
+  // the commit lag (H_CL, every S and role) where it fits; the row is written too
+  if (g.committed <= g.last_index) h = h_with_cl(h, cl_of(g.last_index, g.committed));
   return h;
 }
 __host__ __device__ inline void set_header(gr_peer& g, uint32_t S, uint64_t h) {
@@ -59,7 +61,9 @@ __host__ __device__ inline void set_header(gr_peer& g, uint32_t S, uint64_t h) {
 
 // The header's sync bits (gr_layout.h): the rows they cover are stale and the
 // values follow from lastIndex. Applied after every row of g has been set.
+// The commit lag field (H_CL, every S) resolves committed the same way.
 __host__ __device__ inline void resolve_sync(gr_peer& g, uint32_t S, uint64_t h) {
+  g.committed = h_committed(h, g.last_index, g.committed);
   if (!has_sync_bits((int)S)) return;  // wider groups: those header bits are remote state
   for (uint32_t j = 0; j < S; ++j) {
     if (h_nx(h, j)) g.remotes[j].next = g.last_index + 1;
@@ -406,7 +410,7 @@ __host__ __device__ inline gr_peer_result make_result(const LaneBase& L, const S
       }
     }
   }
-  pr.committed = st.u64(SR_COMMITTED)[p];
+  pr.committed = h_committed(st.u64(SR_HDR)[p], pr.last_index, st.u64(SR_COMMITTED)[p]);
   pr.save_from = save_from(st.u64(SR_SAVED_TO)[p], st.u64(SR_MARKER)[p], pr.last_index);
   pr.term = st.u64(SR_TERM)[p];
   pr.vote = st.u64(SR_VOTE)[p];
@@ -420,7 +424,8 @@ __host__ __device__ inline gr_peer_result make_result(const LaneBase& L, const S
 // of stable_log_to lies below the term-run window; nothing is written then.
 __host__ __device__ inline int32_t commit_marks(const StateBase& st, uint32_t p, const gr_update_commit& u) {
   uint64_t mk = st.u64(SR_MARKER)[p], sv = st.u64(SR_SAVED_TO)[p], ap = st.u64(SR_LOG_APPLIED)[p];
-  const uint64_t last = st.u64(SR_LAST_INDEX)[p], committed = st.u64(SR_COMMITTED)[p];
+  const uint64_t last = st.u64(SR_LAST_INDEX)[p];
+  const uint64_t committed = h_committed(st.u64(SR_HDR)[p], last, st.u64(SR_COMMITTED)[p]);
   const bool inmem = last + 1 > mk;  // len(entries) > 0
   if (u.stable_log_to > 0) {
     const uint64_t i = u.stable_log_to;

@@ -1392,7 +1392,9 @@ __global__ void compact_rows(StateBase st, const uint32_t* slots, const uint64_t
     // the run bits are cleared (the covering run may now start above committed);
     // with S > 6 those header bits are slot 7's rb field and stay
     const uint64_t rmask = has_run_bits((int)st.S) ? H_RUN_MASK : 0ull;
-    st.u64(SR_HDR)[p] = h_make(h_state(h), h_self(h), nn, ge, h_flags(h), h_ric(h), h_rb(h)) & ~rmask;
+    // the commit lag field (H_CL) stays: neither lastIndex nor committed moves here
+    st.u64(SR_HDR)[p] =
+        (h_make(h_state(h), h_self(h), nn, ge, h_flags(h), h_ric(h), h_rb(h)) & ~rmask) | (h & H_CL_MASK);
   }
 }
 

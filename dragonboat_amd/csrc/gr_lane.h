@@ -166,10 +166,10 @@ struct Lane {
       flags = h_flags(hdr0);
       self = h_self(hdr0);
       term = s64(SR_TERM);
-      committed = s64(SR_COMMITTED);
-      committed0 = committed;
       hi = s64(SR_LAST_INDEX);
       hi_ld = hi;
+      committed = h_committed(hdr0, hi, s64(SR_COMMITTED));  // the lag field (gr_layout.h H_CL)
+      committed0 = committed;
     }
     if (miss & G_ETICK) etick = s64(SR_ETICK);
     if (miss & G_LID) leader_id = s64(SR_LEADER_ID);
@@ -245,6 +245,10 @@ struct Lane {
       need(G_REM);
       dirty |= D_REM;
     }
+    // The commit lag field (gr_layout.h H_CL) holds only while lastIndex and
+    // committed do: a pass that changes either writes the row and clears it.
+    const bool uncl = h_cl(hdr0) && (dirty & (D_HI | D_COMMITTED));
+    if (uncl) dirty |= D_COMMITTED;
     if (dirty & (D_LTT | D_ETICK | D_LEADER)) {  // device-internal flag bits (gr_layout.h)
       need(G_CORE);
       uint32_t nf = flags;
@@ -320,7 +324,7 @@ struct Lane {
     // one header word for the small fields; the run bits follow term, committed
     // and the window (gr_layout.h)
     const uint32_t hdr_dirty = D_STATE | D_FLAGS | D_WIN | D_REM | D_RI |
-                               (has_run_bits(S) ? (D_TERM | D_COMMITTED | D_HI) : 0u);
+                               (has_run_bits(S) ? (D_TERM | D_COMMITTED | D_HI) : 0u) | (uncl ? D_COMMITTED : 0u);
     if (dirty & hdr_dirty) {
       uint64_t h = hdr0;
       const uint64_t remmask = ((1ull << (5 * S)) - 1) << H_REM_SHIFT;
@@ -336,7 +340,7 @@ struct Lane {
       }
       const uint64_t rbits = (dirty & D_REM) ? rb : (h_rb(h) & ((1ull << (5 * S)) - 1));
       h = h_make(state, self, nr, gelo, flags, (dirty & D_RI) ? ric : h_ric(h), 0) | keep_rem |
-          (rbits << H_REM_SHIFT);
+          (rbits << H_REM_SHIFT) | (uncl ? 0ull : hdr0 & H_CL_MASK);
       if (has_run_bits(S)) {
         h &= ~H_RUN_MASK;
         if (loaded & G_WIN) {

@@ -96,7 +96,8 @@ __host__ __device__ inline uint32_t run_row(uint32_t n, uint32_t r) { return GR_
 // ---------------------------------------------------------------- header word
 //   bits 0-1 state, 2-5 self slot (15 = none), 6-8 n_runs, 9 H_GE_LO (the newest
 //   run starts at or above firstIndex-1), 10-17 flags (GR_F_* and the device
-//   bits below), 18-20 ReadIndex FIFO count, 24 + 5j remote slot j:
+//   bits below), 18-20 ReadIndex FIFO count, 21-23 the commit lag (H_CL,
+//   below; h_make leaves it 0), 24 + 5j remote slot j:
 //   state (2 bits), active (1), kind (2) -- the `rb` word of gr_lane.h.
 constexpr uint32_t H_SELF_SHIFT = 2, H_NRUNS_SHIFT = 6, H_GE_LO_BIT = 9, H_FLAGS_SHIFT = 10, H_RIC_SHIFT = 18,
                    H_REM_SHIFT = 24;
@@ -140,6 +141,43 @@ __host__ __device__ constexpr bool has_sync_bits(int S) { return S <= 3; }
 __host__ __device__ inline bool h_nx(uint64_t h, uint32_t j) { return (h >> (H_NX_SHIFT + j)) & 1u; }
 __host__ __device__ inline bool h_ms(uint64_t h) { return (h >> H_MS_BIT) & 1u; }
 __host__ __device__ inline bool h_mp(uint64_t h, uint32_t j) { return (h >> (H_MP_SHIFT + j)) & 1u; }
+// Commit lag (every S; bits 21-23, between the FIFO count and rb): a field
+// v >= 1 says committed == lastIndex - (v - 1) and the SR_COMMITTED row is
+// stale; v == 0 says the row is exact. It covers lags 0-6. In the pipelined
+// steady state, one proposal per round in flight, the lag is the same after
+// every pass, for both roles:
+//   leader: before the pass match[j] = lastIndex - 2 (H_MP); the acks raise the
+//   median to hi0 - 1 and the proposal makes lastIndex = hi0 + 1, so committed
+//   = lastIndex - 2 again;
+//   follower: the shared Replicate pair carries LogIndex = hi0, Commit = hi0 - 1
+//   and one entry, so lastIndex = hi0 + 1 and committed = hi0 - 1 = lastIndex - 2.
+// A steady lane whose lag does not change therefore neither loads nor stores
+// the row, and stores no header either. The field is not in H_SYNC_MASK:
+// followers carry it too.
+// Writers of lastIndex or committed: the steady lanes and FastLane keep the
+// field (they set it whenever the final lag fits, else write the row and clear
+// it); the tick lane moves committed only and does the same; the general lane
+// (Lane::store) writes the row and clears the field whenever it changes either
+// value; load (host::header_of) sets it where the record's lag fits and writes
+// the row too. Every reader resolves through h_committed: both lanes above,
+// make_result, commit_marks, sync (host::resolve_sync) and check_state.
+// gr_compact_log rewrites the header and keeps the field (it moves neither value).
+constexpr uint32_t H_CL_SHIFT = 21, H_CL_MAX_LAG = 6;
+constexpr uint64_t H_CL_MASK = 7ull << H_CL_SHIFT;
+__host__ __device__ inline uint32_t h_cl(uint64_t h) { return (uint32_t)(h >> H_CL_SHIFT) & 7u; }
+// the field for these values (0: the lag does not fit, the row must be exact)
+__host__ __device__ inline uint32_t cl_of(uint64_t last_index, uint64_t committed) {
+  const uint64_t lag = last_index - committed;
+  return lag <= H_CL_MAX_LAG ? (uint32_t)lag + 1u : 0u;
+}
+__host__ __device__ inline uint64_t h_with_cl(uint64_t h, uint32_t v) {
+  return (h & ~H_CL_MASK) | ((uint64_t)v << H_CL_SHIFT);
+}
+// committed of a peer whose header is h, lastIndex last_index and SR_COMMITTED row `row`
+__host__ __device__ inline uint64_t h_committed(uint64_t h, uint64_t last_index, uint64_t row) {
+  const uint32_t v = h_cl(h);
+  return v ? last_index - (v - 1u) : row;
+}
 // Run bits (S <= 6; above rb and the sync bits): H_RTT says the window's newest
 // run has the current term, H_RLC that it starts at or below committed. Both
 // hold in steady state (the leader's term's run began before the commit point),

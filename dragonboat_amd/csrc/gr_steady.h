@@ -98,7 +98,6 @@ struct SteadyLeader : SteadyBase<RM> {
     // ---- one load round
     const uint64_t hdr = ntld(B::s64(SR_HDR));
     const uint64_t term = ntld(B::s64(SR_TERM));
-    const uint64_t committed0 = ntld(B::s64(SR_COMMITTED));
     const uint64_t hi0 = ntld(B::s64(SR_LAST_INDEX));
     const uint32_t lw = kp.has_locals ? ntld(kp.ln.u32(LR_LWORD)[i]) : 0u;
     uint32_t cb[S], mt[S];
@@ -120,6 +119,11 @@ struct SteadyLeader : SteadyBase<RM> {
       if (gin[j] != NOPOS && mb_n(cb[j]) >= 2 && !mb_shared(cb[j]))
         x[j][1] = ntld(B::min_at(gin[j]).u64(1, MF_LOG_INDEX));
     }
+    // committed follows from lastIndex and the header's lag field (H_CL); only a
+    // lane whose field is clear loads the row, with that second round
+    const uint32_t cl0 = h_cl(hdr);
+    uint64_t committed0 = hi0 - (uint64_t)(cl0 - 1u);
+    if (cl0 == 0) committed0 = ntld(B::s64(SR_COMMITTED));
     // ---- preconditions (see the header comment)
     const uint32_t self = h_self(hdr), flags = h_flags(hdr);
     const uint64_t rb = h_rb(hdr);
@@ -171,18 +175,24 @@ struct SteadyLeader : SteadyBase<RM> {
     if (!ok) return false;
     // ---- stores
     const uint64_t hi = hi0 + np;  // the proposal's entry (no new run: the newest one is at term)
-    if (c != committed0) ntst(B::s64(SR_COMMITTED), c);
+    // the lag after the pass: the same as before it in steady state (gr_layout.h
+    // H_CL), and then neither the row nor the header is stored; another lag that
+    // fits goes into the header; one that does not is the row's
+    const uint32_t cl = cl_of(hi, c);
+    if (!cl && (cl0 || c != committed0)) ntst(B::s64(SR_COMMITTED), c);
     if (np) ntst(B::s64(SR_LAST_INDEX), hi);
     // match[self] = lastIndex and every next = lastIndex + 1 again (H_MS, H_NX
     // hold); a follower's match is lastIndex - 2 again when its acks were for the
     // entry two proposals back (H_MP holds, nothing stored), else its row is
     // written and its bit cleared
-    uint64_t nh = hdr;
+    uint64_t nh = h_with_cl(hdr, cl);
+    bool synced = true;
 #pragma unroll
     for (int j = 0; j < S; ++j) {
       if ((uint32_t)j == hself || m[j] == hi - 2) continue;
       ntst(B::s64(Rw::MATCH + j), m[j]);
       nh &= ~(1ull << (H_MP_SHIFT + j));
+      synced = false;
     }
     if (nh != hdr) ntst(B::s64(SR_HDR), nh);
     // one commit broadcast and the proposal: both carry LogIndex = the old
@@ -226,7 +236,7 @@ struct SteadyLeader : SteadyBase<RM> {
     ls->leader_out = nmo;
     ls->entries = 0;
     // FastLane::role_hint: WH_SYNC only while every member row is stale
-    *hint_out = (nmi || np) ? ((nh == hdr ? WH_STEADY_LEADER : (WH_LEADER | WH_RUNS)) | (self << WH_SLOT_SHIFT)) : 0u;
+    *hint_out = (nmi || np) ? ((synced ? WH_STEADY_LEADER : (WH_LEADER | WH_RUNS)) | (self << WH_SLOT_SHIFT)) : 0u;
     GR_COVER(STEADY_LEADER);
     return true;
   }
@@ -246,7 +256,6 @@ struct SteadyFollower : SteadyBase<RM> {
     // ---- one load round
     const uint64_t hdr = ntld(B::s64(SR_HDR));
     const uint64_t term = ntld(B::s64(SR_TERM));
-    const uint64_t committed0 = ntld(B::s64(SR_COMMITTED));
     const uint64_t hi0 = ntld(B::s64(SR_LAST_INDEX));
     const uint32_t lw = kp.has_locals ? ntld(kp.ln.u32(LR_LWORD)[i]) : 0u;
     uint32_t other = 0;  // messages from any slot but hL
@@ -274,6 +283,10 @@ struct SteadyFollower : SteadyBase<RM> {
       li[1] = ntld(mb.u64(1, MF_LOG_INDEX));
       cd[1] = ntld(mb.t32(1, MT_CDELTA));
     }
+    // committed from the header's lag field (H_CL); the row only where it is clear
+    const uint32_t cl0 = h_cl(hdr);
+    uint64_t committed0 = hi0 - (uint64_t)(cl0 - 1u);
+    if (cl0 == 0) committed0 = ntld(B::s64(SR_COMMITTED));
     // ---- preconditions
     const uint32_t flags = h_flags(hdr);
     const uint32_t c = mb_n(cbL);
@@ -306,7 +319,11 @@ struct SteadyFollower : SteadyBase<RM> {
     }
     if (!ok) return false;
     // ---- stores
-    if (committed != committed0) ntst(B::s64(SR_COMMITTED), committed);
+    // the lag after the pass (gr_layout.h H_CL): unchanged in steady state, and
+    // then neither the row nor the header is stored
+    const uint32_t cl = cl_of(hi, committed);
+    if (!cl && (cl0 || committed != committed0)) ntst(B::s64(SR_COMMITTED), committed);
+    if (cl != cl0) ntst(B::s64(SR_HDR), h_with_cl(hdr, cl));
     if (hi != hi0) ntst(B::s64(SR_LAST_INDEX), hi);
 #pragma unroll
     for (int j = 0; j < S; ++j) {

@@ -261,6 +261,7 @@ struct TickLane {
     flags = h_flags(hdr);
     nruns = h_nruns(hdr);
     gelo = h_gelo(hdr);
+    committed = h_committed(hdr, hi, committed);  // the lag field (gr_layout.h H_CL): the row may be stale
     tclk[0] = lane_clock(kp);
     uint32_t lf = 0, nt = 0, nq = 0, np = 0;
     if (kp.has_locals) {
@@ -454,7 +455,14 @@ struct TickLane {
     }
     if (!ok) return false;
     // ---- stores
-    if (committed != committed0) s64(SR_COMMITTED) = committed;
+    // committed moved (a heartbeat's Commit; lastIndex never moves here): a lag
+    // that fits goes into the header's field (H_CL), else the row is written and
+    // the field cleared; unmoved, the field stays
+    uint32_t cl = h_cl(hdr);
+    if (committed != committed0) {
+      cl = cl_of(hi, committed);
+      if (!cl) s64(SR_COMMITTED) = committed;
+    }
     uint32_t nf = flags;
     if (etick != etick0) {
       s64(SR_ETICK) = etick;
@@ -489,6 +497,7 @@ struct TickLane {
         }
       }
     }
+    nh = h_with_cl(nh, cl);
     if (nh != hdr) s64(SR_HDR) = nh;
 #pragma unroll
     for (int j = 0; j < S; ++j)
