@@ -43,7 +43,8 @@ namespace gr {
   X(ESC_CAPACITY) X(ESC_SNAPSHOT) X(ESC_ENTRY_SIZE) X(ESC_MSG_RUNS) X(ESC_NONMEMBER)            \
   X(ESC_CONFIG_CHANGE) X(ESC_WIDE_TERM)                                                          \
   X(BAD_COMMITTED_PAST_LAST) X(BAD_RUNS_NOT_ASCENDING) X(BAD_RUN_TERMS_DECREASE)                \
-  X(BAD_WINDOW_PAST_LAST) X(BAD_LAST_TERM_ABOVE_TERM) X(BAD_MARKER_PAST_LAST)
+  X(BAD_WINDOW_PAST_LAST) X(BAD_LAST_TERM_ABOVE_TERM) X(BAD_MARKER_PAST_LAST)                   \
+  X(BAD_STEADY_STATS_RANGE)
 
 #define GR_COVER_ENUM(n) CV_##n,
 enum CoverId : uint32_t { GR_COVER_IDS(GR_COVER_ENUM) CV_N };
@@ -123,7 +124,11 @@ __host__ __device__ static inline void cover_hit(uint32_t id) {
 // logentry.go:314-323), term-run starts strictly ascending with non-decreasing
 // terms (checkEntriesToAppend, entryutils.go:36-48), the newest run inside the
 // log, the last entry's term at most the current term, and inMemory's marker at
-// most lastIndex + 1. A violation counts its BAD_* id.
+// most lastIndex + 1. A violation counts its BAD_* id. BAD_STEADY_STATS_RANGE:
+// a closed-form lane (gr_steady.h) counted more than the bit planes hold that
+// the steady kernel sums its waves' counters in (kSteady*Bits). It sits in this
+// table, not in one of its own, because every checked-build test already
+// requires this table's BAD_* ids to stay 0, on the host lane and on the device.
 #ifdef GR_COVERAGE
 template <class StateBaseT>
 __host__ __device__ inline void check_state(const StateBaseT& st, uint32_t p) {

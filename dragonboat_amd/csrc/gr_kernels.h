@@ -54,6 +54,53 @@ __device__ inline __attribute__((always_inline)) void block_stats(const StepPara
   }
 }
 
+// The sum over the wave of a value below 2^BITS: one ballot and one scalar
+// population count per bit plane, no cross-lane data movement.
+template <int BITS>
+__device__ inline __attribute__((always_inline)) uint32_t wave_sum_bits(uint32_t v) {
+  uint32_t s = 0;
+#pragma unroll
+  for (int b = 0; b < BITS; ++b) s += (uint32_t)__popcll(__ballot((v >> b) & 1u)) << b;
+  return s;
+}
+// block_stats for a wave of the steady kernel's closed-form lanes (gr_steady.h),
+// the same totals into the same rows. Such a wave has one role (lead, from its
+// hint) and its lanes' counters are tiny (gr_steady.h kSteady*Bits), so the nine
+// butterflies (43 LDS and 74 of 477 vector instructions per wave by the SQ
+// counters, profiles/steady_pairs/) shrink to seven bit planes for a
+// leader wave (leader_in / leader_out equal msgs_in / msgs_out, entries = 0)
+// and five for a follower wave (msgs_out = msgs_in, leader_in = leader_out = 0);
+// escalated = bailed = 0, and a lane the closed form did not finish counts
+// nothing. A/B in one call: 0.0574 vs 0.0612 ms per 1M x 3 pass
+// (profiles/steady_pairs/ab.json).
+#ifndef GR_STEADY_BIT_STATS
+#define GR_STEADY_BIT_STATS 1  // A/B builds: 0 = block_stats on the steady path too
+#endif
+__device__ inline __attribute__((always_inline)) void steady_stats(const StepParams& kp, const LaneStats& ls, bool lead) {
+  uint32_t commits, in, out, ent = 0;
+  if (lead) {  // wave-uniform
+    commits = wave_sum_bits<1>(ls.leader_commit);
+    in = wave_sum_bits<kSteadyLeaderMsgBits>(ls.msgs_in);
+    out = wave_sum_bits<kSteadyLeaderMsgBits>(ls.msgs_out);
+  } else {
+    commits = wave_sum_bits<1>(ls.follower_commit);
+    in = out = wave_sum_bits<kSteadyFollowerMsgBits>(ls.msgs_in);
+    ent = wave_sum_bits<kSteadyFollowerMsgBits>(ls.entries);
+  }
+  // lane k adds total k: commits, in, out, then a leader wave its leader_in and
+  // leader_out, a follower wave its entries
+  const uint32_t k = threadIdx.x & 63;
+  if (k < 5u) {
+    const uint32_t v = k == 0 ? commits : k == 1 ? in : k == 2 ? out : lead ? (k == 3 ? in : out) : (k == 3 ? ent : 0u);
+    const uint32_t f = k == 0 ? (lead ? (uint32_t)ST_LEADER_COMMITS : (uint32_t)ST_FOLLOWER_COMMITS)
+                     : k == 1 ? (uint32_t)ST_MSGS_IN
+                     : k == 2 ? (uint32_t)ST_MSGS_OUT
+                     : lead ? (k == 3 ? (uint32_t)ST_LEADER_MSGS_IN : (uint32_t)ST_LEADER_MSGS_OUT)
+                            : (uint32_t)ST_REPLICATE_ENTRIES;
+    if (v) atomicAdd((unsigned long long*)(kp.stats + (uint64_t)blockIdx.x * NSTAT + f), (unsigned long long)v);
+  }
+}
+
 // Pass 1: every lane runs the lean steady-state lane (gr_fast.h). Lanes that
 // meet anything else store no state and are appended to one of kBailLists
 // lists (followers: list = workgroup % 8, leaders: 8 + workgroup % 8; one returning atomic per wave and role with a
@@ -562,21 +609,31 @@ __global__ __launch_bounds__(kBlock, GR_FAST_MIN_WAVES) void gr_steady_kernel(St
   if ((threadIdx.x & 63) == 0) wave_flags(bail_list, list_cap)[wave] = 0;
   LaneStats ls;
   bool done = false;
-  uint32_t myhint = 0, role = 0;
+  uint32_t myhint = 0;
   const bool active = i < kp.n_lanes;
+  const bool lead = S == 3 && steady_leader_hint(hint);  // wave-uniform: the wave's role is its hint's
   if (active) {
     if constexpr (S == 3) {
-      if (steady_leader_hint(hint)) {
-        role = GR_LEADER;
-        done = SteadyLeader<S, RM>(kp, i, i).step(&ls, hint, &myhint);
-      }
+      if (lead) done = SteadyLeader<S, RM>(kp, i, i).step(&ls, hint, &myhint);
     }
     if (steady_follower_hint(hint)) done = SteadyFollower<S, RM>(kp, i, i).step(&ls, hint, &myhint);
     if (done) GR_CHECK_STATE(kp.st, i);
   }
   // lanes not finished here (nothing stored) go to FastLane in the role
   // instances that follow (lists 24..31), not straight to the general kernel
-  wave_finish<S>(kp, i, wave, true, active, false, false, role, myhint, ls, bail_list, counters, list_cap);
+#if GR_STEADY_BIT_STATS
+  if (kp.hints) {
+    // wave_finish's hint for a wave that is all this kernel's: a lane the closed
+    // form left (hint 0, on to FastLane) is a wildcard like an idle one
+    const uint64_t act = __ballot(active);
+    const uint32_t nh = wave_hint(active, myhint, act);
+    if ((threadIdx.x & 63) == 0 && act) kp.hints_out[wave] = (uint8_t)nh;
+  }
+  if (kp.stats) steady_stats(kp, ls, lead);
+#else
+  wave_finish<S>(kp, i, wave, true, active, false, false, lead ? (uint32_t)GR_LEADER : 0u, myhint, ls, bail_list,
+                 counters, list_cap);
+#endif
   bail_append(active && !done, kRetryList0 + blockIdx.x % 8, bail_list, counters, list_cap, i);
 }
 

@@ -68,6 +68,16 @@ __host__ __device__ inline bool steady_hint(uint32_t h) {
   return (S == 3 && steady_leader_hint(h)) || steady_follower_hint(h);
 }
 
+// Bit widths of a finished closed-form lane's counters (LaneStats), which the
+// steady kernel sums per wave as bit planes (gr_kernels.h steady_stats):
+//   leader (S = 3): msgs_in <= 4 (two acks from each follower), msgs_out =
+//   nout * (S - 1) with nout <= kUniformMax; follower: msgs_in = msgs_out = c
+//   <= 2, entries <= c; the commit counters are 0 or 1, the rest 0.
+// The preconditions enforce them; the checked build counts a lane outside them
+// (BAD_STEADY_STATS_RANGE).
+constexpr int kSteadyLeaderMsgBits = 3, kSteadyFollowerMsgBits = 2;
+static_assert(kUniformMax * 2 < (1u << kSteadyLeaderMsgBits), "a steady leader's msgs_out (S = 3) must fit");
+
 template <int RM>
 struct SteadyBase {
   static constexpr bool kOneChunk = RM == RT_LOOPBACK;
@@ -235,6 +245,7 @@ struct SteadyLeader : SteadyBase<RM> {
     ls->leader_in = nmi;
     ls->leader_out = nmo;
     ls->entries = 0;
+    GR_CHECK_INV(nmi < (1u << kSteadyLeaderMsgBits) && nmo < (1u << kSteadyLeaderMsgBits), BAD_STEADY_STATS_RANGE);
     // FastLane::role_hint: WH_SYNC only while every member row is stale
     *hint_out = (nmi || np) ? ((synced ? WH_STEADY_LEADER : (WH_LEADER | WH_RUNS)) | (self << WH_SLOT_SHIFT)) : 0u;
     GR_COVER(STEADY_LEADER);
@@ -351,6 +362,7 @@ struct SteadyFollower : SteadyBase<RM> {
     ls->leader_in = 0;
     ls->leader_out = 0;
     ls->entries = nent;
+    GR_CHECK_INV(c < (1u << kSteadyFollowerMsgBits) && nent < (1u << kSteadyFollowerMsgBits), BAD_STEADY_STATS_RANGE);
     *hint_out = c ? (WH_FOLLOWER | WH_RUNS | (hL << WH_SLOT_SHIFT)) : 0u;  // FastLane::role_hint
     GR_COVER(STEADY_FOLLOWER);
     return true;
