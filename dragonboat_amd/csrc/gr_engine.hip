@@ -80,7 +80,7 @@ struct gr_engine {
   LaneBase ln{};
   uint64_t* stats = nullptr;
   uint32_t stats_rows = 0;
-  uint32_t* bail = nullptr;      // kBailLists lists of cap lanes each, then the wave lists (bail_words)
+  uint32_t* bail = nullptr;      // kBailLists lists of cap lanes each, then the tick lists (bail_words)
   uint64_t* tick_stage = nullptr;  // a TickStage record per tick-list entry (gr_layout.h)
   uint32_t* counters = nullptr;  // [2 (pass parity)][kCounters][kCounterStride]
   // gr_step_device passes of at least this many lanes run the role instances
@@ -106,8 +106,7 @@ struct gr_engine {
   // GR_WAVE_CLOCK=<path> at gr_create (profiling): the general kernel records
   // each wave's span; gr_destroy writes the last pass's records to <path>
   uint64_t* wclock = nullptr;
-  uint8_t bin_general = 1;  // StepParams::bin_general (GR_BIN_GENERAL=0 at gr_create: off, A/B runs)
-  uint32_t* tail_hint = nullptr;  // StepParams::tail_hint: pinned, host-visible (GR_TAIL_HINT=0: off)
+  uint32_t* tail_hint = nullptr;  // StepParams::tail_hint: pinned, host-visible
   uint8_t tail_mode = 0;          // StepParams::tail_mode (GR_TAIL_MODE at gr_create: tests, A/B runs)
   uint8_t elections = 0;          // StepParams::elections (gr_set_elections; GR_ELECTIONS=1 at gr_create)
   // the promotion list (gr_promotions): a 16-byte header (count, overflow flag)
@@ -241,7 +240,6 @@ StepParams base_params(gr_engine* e) {
   kp.max_entry_size = e->cfg.max_entry_size;
   kp.small_blocks = e->small_blocks;
   kp.wclock = e->wclock;
-  kp.bin_general = e->bin_general;
   kp.tail_hint = e->tail_hint;
   kp.tail_mode = e->tail_mode;
   kp.tick_stage = e->tick_stage;
@@ -451,8 +449,10 @@ int gr_create(const gr_config* cfg, gr_engine** out) {
     if (v > 0) e->split_min = (uint32_t)v;
   }
   if (const char* sb = getenv("GR_SMALL_BLOCKS")) e->small_blocks = (uint32_t)strtoul(sb, nullptr, 10);
-  if (const char* bg = getenv("GR_BIN_GENERAL")) e->bin_general = bg[0] == '1';
-  if (const char* tm = getenv("GR_TAIL_MODE")) e->tail_mode = (uint8_t)(strtoul(tm, nullptr, 10) & 3u);
+  if (const char* tm = getenv("GR_TAIL_MODE")) {
+    const unsigned long v = strtoul(tm, nullptr, 10);
+    if (v <= 2) e->tail_mode = (uint8_t)v;
+  }
   if (const char* el = getenv("GR_ELECTIONS")) e->elections = el[0] == '1';
   const char* qd = getenv("GR_QUIESCE_ON_DEVICE");
   if (const char* wc = getenv("GR_WAVE_CLOCK")) {
@@ -488,13 +488,11 @@ int gr_create(const gr_config* cfg, gr_engine** out) {
     gr_destroy(e);
     return GR_EDEVICE;
   }
-  const char* th = getenv("GR_TAIL_HINT");
-  if (!(th && th[0] == '0')) {  // a failed allocation only leaves the grids full
-    if (hipHostMalloc((void**)&e->tail_hint, 64, hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess)
-      e->tail_hint = nullptr;
-    else
-      *(volatile uint32_t*)e->tail_hint = kTailAll;
-  }
+  // a failed allocation only leaves every launch on
+  if (hipHostMalloc((void**)&e->tail_hint, 64, hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess)
+    e->tail_hint = nullptr;
+  else
+    *(volatile uint32_t*)e->tail_hint = kTailAll;
   if (qd && qd[0] == '1') {
     const int r = ensure_quiesce(e);
     if (r) {

@@ -53,6 +53,18 @@ __device__ inline __attribute__((always_inline)) void block_stats(const StepPara
     if (v) atomicAdd((unsigned long long*)(kp.stats + (uint64_t)bid * NSTAT + f), (unsigned long long)v);
   }
 }
+// A list walker's running totals of the tick and general lanes: every field but
+// bailed, which its kernel counts.
+__device__ inline __attribute__((always_inline)) void stats_add(LaneStats& acc, const LaneStats& ls) {
+  acc.leader_commit += ls.leader_commit;
+  acc.follower_commit += ls.follower_commit;
+  acc.escalated += ls.escalated;
+  acc.msgs_in += ls.msgs_in;
+  acc.msgs_out += ls.msgs_out;
+  acc.leader_in += ls.leader_in;
+  acc.leader_out += ls.leader_out;
+  acc.entries += ls.entries;
+}
 
 // The sum over the wave of a value below 2^BITS: one ballot and one scalar
 // population count per bit plane, no cross-lane data movement.
@@ -73,9 +85,6 @@ __device__ inline __attribute__((always_inline)) uint32_t wave_sum_bits(uint32_t
 // escalated = bailed = 0, and a lane the closed form did not finish counts
 // nothing. A/B in one call: 0.0574 vs 0.0612 ms per 1M x 3 pass
 // (profiles/steady_pairs/ab.json).
-#ifndef GR_STEADY_BIT_STATS
-#define GR_STEADY_BIT_STATS 1  // A/B builds: 0 = block_stats on the steady path too
-#endif
 __device__ inline __attribute__((always_inline)) void steady_stats(const StepParams& kp, const LaneStats& ls, bool lead) {
   uint32_t commits, in, out, ent = 0;
   if (lead) {  // wave-uniform
@@ -102,29 +111,20 @@ __device__ inline __attribute__((always_inline)) void steady_stats(const StepPar
 }
 
 // Pass 1: every lane runs the lean steady-state lane (gr_fast.h). Lanes that
-// meet anything else store no state and are appended to one of kBailLists
-// lists (followers: list = workgroup % 8, leaders: 8 + workgroup % 8; one returning atomic per wave and role with a
-// bailing lane, a wave's lanes contiguous and ascending). Spreading the
-// appends over 16 counters 256 B apart keeps them from serialising when every
-// wave bails a few lanes (one shared counter: 105 us instead of 37 us on
-// config 3); no barrier, so waves of steady-state populations retire freely.
+// meet anything else store no state and are appended to a list (one returning
+// atomic per wave and list with an appending lane, a wave's lanes contiguous and
+// ascending). The counters are 256 B apart, so the appends do not serialise when
+// every wave hands over a few lanes (one shared counter: 105 us instead of 37 us
+// on config 3); no barrier, so waves of steady-state populations retire freely.
 // Lists 0..31 are the general kernel's, keyed by handler class (general_bin:
 // list = class x 2 + workgroup parity), so that kernel, walking them in order,
-// runs waves of one class (fewer divergent handler paths per wave); with
-// StepParams::bin_general off, by role and workgroup (followers 0..15, leaders
-// 16..31). The tick lists are below.
-// Lists 32..39: lanes a split pass's steady kernel did not finish, which the
-// role instances step with FastLane before anything goes to the general kernel.
-// After the lane lists' storage: one flag byte and one lane mask per wave, the
-// waves a split pass's steady kernel leaves to the role instances (flag =
-// WF_LISTED | the wave's hint as the pass started; mask = its lanes still to
-// step: the steady kernel finishes quiesced lanes itself and sends lanes with
-// ticks or a ReadIndex straight to the tick lists). Every wave's flag is
-// rewritten every split pass, so no counter or atomic is involved: the role
-// instances scan the flags, 64 waves per load, instead of launching one
-// workgroup per 256 lanes, most of which would find nothing to do.
+// runs waves of one class (fewer divergent handler paths per wave).
+// Lists 32..39 (retry lists, list = 32 + workgroup % 8): lanes a split pass's
+// steady kernel did not finish, which the role instances step with FastLane
+// before anything goes to the general kernel; in a pass without role instances
+// the general kernel walks them with its own (GM_RETRY).
 // The tick lists (lanes with ticks or a ReadIndex for the tick kernel) are
-// kTickLists shorter lists after the wave masks: a lane of 256-lane block b (or
+// kTickLists shorter lists after the lane lists: a lane of 256-lane block b (or
 // retry entry x of block x / 256) goes to list b % kTickLists, so a list never
 // holds more than tick_cap lanes. Config 3 appends from every one of its ~7.8k
 // waves (10% of its groups are active, scattered); one returning atomic word
@@ -137,43 +137,28 @@ constexpr uint32_t kGeneralWaveSlots = 4096;
 constexpr uint32_t kBailLists = 40, kGeneralLists = 32, kRetryList0 = 32,
                    kTickCounter0 = kBailLists, kCounters = kBailLists + kTickLists,
                    kCounterStride = 64;  // counters 256 B apart
-constexpr uint32_t WF_LISTED = 0x80;     // wave flag: the role instances step this wave's masked lanes
-// Word 1 of counter 0's 256-B slot: nonzero when a split pass's steady kernel
-// listed some wave for the role instances (a plain store, no atomic); with it
-// zero and the retry lists empty the role instances return at once. Cleared for
-// the next pass with the counters.
-constexpr uint32_t kListedWord = 1;
-// Word 2: the general kernel's next 64-lane chunk past the grid's first (each
-// wave's first chunk is its own index; a wave that finishes takes the next one
-// with one returning atomic, so a pass with more lanes than the grid's waves
-// holds puts the extra chunks on the waves that finish first). Cleared with the
-// next pass's counters.
+// Word 2 of counter 0's 256-B slot: the general kernel's next 64-lane chunk past
+// the grid's first (each wave's first chunk is its own index; a wave that
+// finishes takes the next one with one returning atomic, so a pass with more
+// lanes than the grid's waves holds puts the extra chunks on the waves that
+// finish first). Cleared with the next pass's counters.
 constexpr uint32_t kGeneralNext = 2;
-// Tail kernel mode (TailPlan): GM_RETRY: the retry lists (32..39) hold lanes no
-// role instance stepped (the steady kernel's no_roles mode), so the general
-// kernel walks lists 0..39, not 0..31.
+// Tail kernel mode (tail_roles): GM_RETRY: the retry lists (32..39) hold lanes no
+// role instance stepped (the steady kernel ran and the role instances did not),
+// so the general kernel walks lists 0..39, not 0..31.
 constexpr uint32_t GM_RETRY = 2;
-__host__ __device__ inline uint64_t wave_flag_words(uint32_t cap) { return ((uint64_t)cap / 64 + 64) / 4 * 2; }
 // Lanes one tick list can receive: the lanes of every kTickLists-th block, from
-// the steady kernel and the listed role waves (keyed by lane), plus as many
-// retry entries (keyed by entry index): twice one key's bound.
+// the steady kernel (keyed by lane), plus as many retry entries (keyed by entry
+// index): twice one key's bound.
 // The steady kernel keys by role as well (leaders to lists 32..63, the rest to
 // 0..31, each half by block % 32), so the bound counts every 32nd block.
 __host__ __device__ inline uint64_t tick_cap(uint32_t cap) {
   return 2 * (((uint64_t)(cap + 255) / 256 + kTickLists / 2 - 1) / (kTickLists / 2) * 256);
 }
-__host__ __device__ inline uint64_t tick_off(uint32_t cap) {
-  return (uint64_t)kBailLists * cap + wave_flag_words(cap) + 2 * ((uint64_t)cap / 64 + 1);
-}
-// u32 words of the list storage: kBailLists lane lists of cap, the wave flags,
-// the wave masks (u64), the kTickLists tick lists of tick_cap
+__host__ __device__ inline uint64_t tick_off(uint32_t cap) { return (uint64_t)kBailLists * cap; }
+// u32 words of the list storage: kBailLists lane lists of cap, then the
+// kTickLists tick lists of tick_cap
 __host__ __device__ inline uint64_t bail_words(uint32_t cap) { return tick_off(cap) + kTickLists * tick_cap(cap); }
-__host__ __device__ inline uint8_t* wave_flags(uint32_t* bail_list, uint32_t cap) {
-  return (uint8_t*)(bail_list + (uint64_t)kBailLists * cap);
-}
-__host__ __device__ inline uint64_t* wave_masks(uint32_t* bail_list, uint32_t cap) {
-  return (uint64_t*)(bail_list + (uint64_t)kBailLists * cap + wave_flag_words(cap));
-}
 
 // One wave's appends to bail list `list`: one returning atomic for the wave,
 // the wave's lanes contiguous and ascending.
@@ -217,7 +202,7 @@ __device__ inline __attribute__((always_inline)) uint64_t tick_append(bool mine,
   return e;
 }
 
-// The general kernel's lane classes (StepParams::bin_general): role, whether a
+// The general kernel's lane classes: role, whether a
 // message from a higher or a lower term waits (a step-down or a term adoption,
 // or a stale message to drop), and whether a mailbox holds full records (rejects,
 // catch-up Replicates, heartbeats) rather than uniform steady traffic. Its loads
@@ -243,20 +228,15 @@ __device__ inline __attribute__((always_inline)) uint32_t general_bin(const Step
   return st * 8 + (higher ? 4u : 0u) + (lower ? 2u : 0u) + (full ? 1u : 0u);
 }
 
-// Hand lane i (peer p) to the general kernel: appended to its class's list
-// (bin_general), else by role and workgroup (lead: a leader lane).
+// Hand lane i (peer p) to the general kernel: appended to its class's list.
 template <int S>
-__device__ inline __attribute__((always_inline)) void general_append(const StepParams& kp, bool mine, bool lead, uint32_t i,
+__device__ inline __attribute__((always_inline)) void general_append(const StepParams& kp, bool mine, uint32_t i,
                                                                      uint32_t p, uint32_t bid, uint32_t* bail_list,
                                                                      uint32_t* counters, uint32_t list_cap) {
   uint64_t bm = __ballot(mine);
   if (!bm) return;
   uint32_t key = 0;
-  if (kp.bin_general) {
-    if (mine) key = general_bin<S>(kp, i, p) * 2 + (bid & 1u);
-  } else {
-    key = (lead ? kGeneralLists / 2 : 0u) + bid % (kGeneralLists / 2);
-  }
+  if (mine) key = general_bin<S>(kp, i, p) * 2 + (bid & 1u);
   // each lane's class-mates (one ballot per class present: register work only),
   // then one returning atomic per class issued by all classes' first lanes in
   // the same instruction, so a wave with several classes waits for one round
@@ -276,19 +256,15 @@ __device__ inline __attribute__((always_inline)) void general_append(const StepP
   if (mine) bail_list[(uint64_t)key * list_cap + base + (uint32_t)__popcll(same & ((1ull << lane) - 1))] = i;
 }
 
-#ifndef GR_FAST_MIN_WAVES
-#define GR_FAST_MIN_WAVES 1  // waves per SIMD the register allocation must allow (A/B builds)
-#endif
-#ifndef GR_LISTED_MIN_WAVES
-#define GR_LISTED_MIN_WAVES 1  // the role instances over listed waves (A/B builds: 4 and 5 spill)
-#endif
 // Role instances. A large pass (StepParams::split) runs R = FL_FOLLOWER and R =
-// FL_LEADER (side by side in one gr_roles_kernel launch by default, in sequence
-// with GR_ROLES_MERGED=0), each with the other role's code and registers compiled
-// out: a wave whose hint (as the pass
-// started) names a role goes to that instance, and an unhinted wave to both, each
+// FL_LEADER, each with the other role's code and registers compiled out and each
 // stepping the lanes of its role and leaving the others untouched (FastLane
-// `take`). A small pass runs the single instance R = FL_ANY, which picks the
+// `take`). After the steady kernel they walk its retry lists, side by side in
+// one gr_roles_kernel launch (roles_listed). A split pass without the steady
+// kernel (gr_step, generic routes, a lane-to-peer table) launches
+// gr_fast_kernel<S, R, RM> for each role over every workgroup: a wave whose hint
+// (as the pass started) names a role goes to that instance, and an unhinted wave
+// to both. A mid-size pass runs the single instance R = FL_ANY, which picks the
 // lean-lane variant per wave from its hint. A block none of whose waves is an
 // instance's returns at once.
 // Measured and dropped: the two instances concurrently on two streams (0.133 vs
@@ -317,15 +293,14 @@ __device__ inline __attribute__((always_inline)) uint32_t wave_hint(bool done, u
 // hint of this wave (its lanes' common role hint when every active lane was
 // stepped here, else 0; written by each instance that stepped a lane of the
 // wave, both write 0 when an unhinted wave's lanes split between them), the
-// bail lists (followers into lists 0..7, leaders into 8..15, lanes with ticks
-// or a ReadIndex into the tick lists (tick_append): the later kernels walk their
-// lists in order, so their waves hold one kind of lane and diverge less), and
-// the stats.
+// hand-over lists (lanes with ticks or a ReadIndex into the tick lists
+// (tick_append), the rest into the general lists by class (general_append): the
+// later kernels walk their lists in order, so their waves hold one kind of lane
+// and diverge less), and the stats.
 template <int S>
 __device__ inline __attribute__((always_inline)) void wave_finish(const StepParams& kp, uint32_t i, uint32_t wave, bool mine, bool active,
-                                   bool skip, bool bail, uint32_t role, uint32_t myhint, const LaneStats& ls,
-                                   uint32_t* bail_list, uint32_t* counters, uint32_t list_cap,
-                                   uint32_t bid = blockIdx.x) {
+                                   bool skip, bool bail, uint32_t myhint, const LaneStats& ls,
+                                   uint32_t* bail_list, uint32_t* counters, uint32_t list_cap) {
   if (kp.hints) {
     // over the lanes that are this kernel's (mine), written by the first of them
     const uint64_t mm = __ballot(mine);
@@ -338,12 +313,11 @@ __device__ inline __attribute__((always_inline)) void wave_finish(const StepPara
       if ((threadIdx.x & 63) == (uint32_t)__ffsll((unsigned long long)mm) - 1 && dn) kp.hints_out[wave] = (uint8_t)nh;
     }
   }
-  const bool lead = role == GR_LEADER;
   const bool tickish = bail && kp.has_locals && (kp.ln.u32(LR_LWORD)[i] & LW_OTHER);
   const uint32_t p = bail && !tickish && kp.has_lane_peer ? kp.ln.u32(LR_LANE_PEER)[i] : i;
-  general_append<S>(kp, bail && !tickish, lead, i, p, bid, bail_list, counters, list_cap);
+  general_append<S>(kp, bail && !tickish, i, p, blockIdx.x, bail_list, counters, list_cap);
   tick_append(tickish, wave * 64, bail_list, counters, list_cap, i, kp.tick_stage);  // the wave's lanes share a block
-  if (kp.stats) block_stats(kp, ls, bid);
+  if (kp.stats) block_stats(kp, ls);
 }
 
 // One wave of a lean-kernel instance: lane i of wave `wave`, whose hint as the
@@ -351,24 +325,23 @@ __device__ inline __attribute__((always_inline)) void wave_finish(const StepPara
 // instance's. Steps the lane, then the wave's hint, bail lists and stats.
 template <int S, int R, int RM>
 __device__ inline __attribute__((always_inline)) void fast_wave(const StepParams& kp, uint32_t i, uint32_t wave, uint32_t hint, int wk, bool mine,
-                                 uint32_t* bail_list, uint32_t* counters, uint32_t list_cap,
-                                 uint32_t bid = blockIdx.x) {
+                                 uint32_t* bail_list, uint32_t* counters, uint32_t list_cap) {
   LaneStats ls;
   bool bail = false, skip = false;
-  uint32_t role = 0, myhint = 0;
+  uint32_t myhint = 0;
   const bool active = mine && i < kp.n_lanes;
   if (active) {
     const uint32_t p = kp.has_lane_peer ? kp.ln.u32(LR_LANE_PEER)[i] : i;
     // leaves ls zero when it bails
     if (R != FL_ANY)
-      bail = !lean_step<S, R, RM>(kp, i, p, &ls, &role, hint, &myhint, wk == FL_ANY ? R : FL_ANY, &skip);
-    else if (wk == FL_FOLLOWER) bail = !fast_step<S, FL_FOLLOWER, RM>(kp, i, p, &ls, &role, hint, &myhint);
-    else if (wk == FL_LEADER) bail = !fast_step<S, FL_LEADER, RM>(kp, i, p, &ls, &role, hint, &myhint);
-    else bail = !fast_step<S, FL_ANY, RM>(kp, i, p, &ls, &role, hint, &myhint);
+      bail = !lean_step<S, R, RM>(kp, i, p, &ls, nullptr, hint, &myhint, wk == FL_ANY ? R : FL_ANY, &skip);
+    else if (wk == FL_FOLLOWER) bail = !fast_step<S, FL_FOLLOWER, RM>(kp, i, p, &ls, nullptr, hint, &myhint);
+    else if (wk == FL_LEADER) bail = !fast_step<S, FL_LEADER, RM>(kp, i, p, &ls, nullptr, hint, &myhint);
+    else bail = !fast_step<S, FL_ANY, RM>(kp, i, p, &ls, nullptr, hint, &myhint);
     bail = bail && !skip;  // a skipped lane is the other instance's
     if (!bail && !skip) GR_CHECK_STATE(kp.st, p);
   }
-  wave_finish<S>(kp, i, wave, mine, active, skip, bail, role, myhint, ls, bail_list, counters, list_cap, bid);
+  wave_finish<S>(kp, i, wave, mine, active, skip, bail, myhint, ls, bail_list, counters, list_cap);
 }
 
 // Locate entry x of the 8 lists whose exclusive prefix is start[0..8]: list and offset.
@@ -383,50 +356,24 @@ __device__ inline __attribute__((always_inline)) void list_at(const uint32_t (&s
   *off = o;
 }
 
-// The role instances of a split pass with the steady kernel (R != FL_ANY): a
-// fixed grid of nblk workgroups (this one is bid) walks the waves the steady
-// kernel listed for this instance (wave flags), one wave of the grid per listed
-// wave, grid-stride, then the lanes it left for FastLane (retry lists).
+// One role instance (R != FL_ANY) of a split pass with the steady kernel: a
+// fixed grid of nblk workgroups (this one is bid) walks the lanes the steady
+// kernel left for FastLane (the retry lists).
 template <int S, int R, int RM>
 __device__ inline __attribute__((always_inline)) void roles_listed(const StepParams& kp, uint32_t* bail_list,
                                                                    uint32_t* counters, uint32_t list_cap,
                                                                    uint32_t bid, uint32_t nblk) {
-  static_assert(R != FL_ANY, "listed waves are the role instances'");
-  // nothing listed and no retry lane (the steady state): return before any
-  // flag is read (wave-uniform scalar loads of words the steady kernel wrote)
+  static_assert(R != FL_ANY, "the retry lanes are the role instances'");
+  // no retry lane (the steady state): return after these wave-uniform scalar
+  // loads of counters the steady kernel wrote
   uint32_t start[9];
   start[0] = 0;
 #pragma unroll
   for (uint32_t l = 0; l < 8; ++l)
     start[l + 1] = start[l] + (uint32_t)__builtin_amdgcn_readfirstlane(counters[(kRetryList0 + l) * kCounterStride]);
   const uint32_t n = start[8];
-  if (!__builtin_amdgcn_readfirstlane(counters[kListedWord]) && n == 0) return;
-  {
-    // grid wave g owns waves g, g + W, g + 2W, ... (W = the grid's waves): it
-    // reads 64 of their flags per load (lane l: wave g + W * (r + l)) and steps
-    // the listed ones of this instance's role (an unhinted wave is both
-    // instances') over the lanes their masks leave
-    const uint8_t* wf = wave_flags(bail_list, list_cap);
-    const uint64_t* wm = wave_masks(bail_list, list_cap);
-    const uint32_t nw = (kp.n_lanes + 63) / 64, lane = threadIdx.x & 63;
-    const uint32_t g = (uint32_t)__builtin_amdgcn_readfirstlane(bid * (kBlock / 64) + (threadIdx.x >> 6));
-    const uint32_t W = nblk * (kBlock / 64);
-    for (uint32_t r = 0; g + (uint64_t)W * r < nw; r += 64) {  // wave-uniform
-      const uint64_t idx = g + (uint64_t)W * (r + lane);
-      const uint32_t f = idx < nw ? (uint32_t)wf[idx] : 0u;
-      const int k = wave_kernel(f & 0x7Fu, S);
-      uint64_t todo = __ballot((f & WF_LISTED) && (R == FL_FOLLOWER ? k != FL_LEADER : k != FL_FOLLOWER));
-      while (todo) {
-        const uint32_t b = (uint32_t)__ffsll((unsigned long long)todo) - 1;
-        todo &= todo - 1;
-        const uint32_t wave = g + W * (r + b), hint = (uint32_t)__shfl((int)f, (int)b) & 0x7Fu;
-        const uint64_t m = wm[wave];
-        fast_wave<S, R, RM>(kp, wave * 64 + lane, wave, hint, wave_kernel(hint, S), (m >> lane) & 1ull, bail_list,
-                            counters, list_cap, bid);
-      }
-    }
-  }
-  // the lanes the steady kernel left (lists 24..31, final: it ran before this
+  if (n == 0) return;
+  // the lanes the steady kernel left (lists 32..39, final: it ran before this
   // launch on the stream), grid-stride; each role instance takes the lanes of
   // its role. No hint is written for them (their waves were the steady kernel's).
   // A wave of list entries may hold lanes of several replica blocks (a wave that
@@ -439,7 +386,7 @@ __device__ inline __attribute__((always_inline)) void roles_listed(const StepPar
   for (uint32_t base = bid * kBlock; base < n; base += nblk * kBlock) {
     const uint32_t x = base + threadIdx.x;
     bool bail = false;
-    uint32_t role = 0, li = 0;
+    uint32_t li = 0;
     if (x < n) {
       uint32_t l, off;
       list_at(start, x, &l, &off);
@@ -447,10 +394,11 @@ __device__ inline __attribute__((always_inline)) void roles_listed(const StepPar
       LaneStats ls;
       bool skip = false;
       uint32_t h = 0;
-      bail = !lean_step<S, R, RM>(kr, li, li, &ls, &role, 0u, &h, R, &skip);
+      bail = !lean_step<S, R, RM>(kr, li, li, &ls, nullptr, 0u, &h, R, &skip);
       bail = bail && !skip;
       if (!bail && !skip) {
         GR_CHECK_STATE(kp.st, li);
+        // not stats_add: that sums `escalated` too, which this kernel has never summed
         acc.leader_commit += ls.leader_commit;
         acc.follower_commit += ls.follower_commit;
         acc.msgs_in += ls.msgs_in;
@@ -460,55 +408,48 @@ __device__ inline __attribute__((always_inline)) void roles_listed(const StepPar
         acc.entries += ls.entries;
       }
     }
-    const bool lead = role == GR_LEADER;
     const bool tickish = bail && kp.has_locals && (kp.ln.u32(LR_LWORD)[li] & LW_OTHER);
-    general_append<S>(kp, bail && !tickish, lead, li, li, bid, bail_list, counters, list_cap);
+    general_append<S>(kp, bail && !tickish, li, li, bid, bail_list, counters, list_cap);
     tick_append(tickish, base, bail_list, counters, list_cap, li, kp.tick_stage);  // keyed by the entry's block
   }
   if (kp.stats && n > bid * kBlock) block_stats(kp, acc, bid);
 }
 
-// LISTED (split passes with the steady kernel, R != FL_ANY): roles_listed over
-// the whole grid. Otherwise one workgroup per 256 lanes, every wave checked
-// against its hint.
-template <int S, int R, int RM, bool LISTED>
-__global__ __launch_bounds__(kBlock, LISTED ? GR_LISTED_MIN_WAVES : GR_FAST_MIN_WAVES) void gr_fast_kernel(StepParams kp, uint32_t* bail_list,
-                                                                             uint32_t* counters, uint32_t list_cap) {
-  static_assert(!LISTED || R != FL_ANY, "listed waves are the role instances'");
-  if constexpr (LISTED) {
-    roles_listed<S, R, RM>(kp, bail_list, counters, list_cap, blockIdx.x, gridDim.x);
-  } else {
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane(i >> 6);
-    // the workgroup's four wave hints in one scalar load (the set the previous
-    // pass wrote; this pass writes the other one), so no lane waits on a vector
-    // load before its first round
-    const uint32_t hw = kp.hints ? sload_u32(kp.hints + (uint64_t)blockIdx.x * (kBlock / 64)) : 0u;
-    const uint32_t hint = (hw >> (8 * (wave & 3))) & 0xFFu;
-    const int wk = wave_kernel(hint, S);  // FL_ANY: unhinted
-    bool mine = true;
-    bool blk = true;  // this block has waves of this instance
-    if (R != FL_ANY) {  // a split pass without the steady kernel
-      bool any = false;
+// One workgroup per 256 lanes, every wave checked against its hint.
+template <int S, int R, int RM>
+__global__ __launch_bounds__(kBlock, 1) void gr_fast_kernel(StepParams kp, uint32_t* bail_list, uint32_t* counters,
+                                                            uint32_t list_cap) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane(i >> 6);
+  // the workgroup's four wave hints in one scalar load (the set the previous
+  // pass wrote; this pass writes the other one), so no lane waits on a vector
+  // load before its first round
+  const uint32_t hw = kp.hints ? sload_u32(kp.hints + (uint64_t)blockIdx.x * (kBlock / 64)) : 0u;
+  const uint32_t hint = (hw >> (8 * (wave & 3))) & 0xFFu;
+  const int wk = wave_kernel(hint, S);  // FL_ANY: unhinted
+  bool mine = true;
+  bool blk = true;  // this block has waves of this instance
+  if (R != FL_ANY) {  // a split pass without the steady kernel
+    bool any = false;
 #pragma unroll
-      for (uint32_t w = 0; w < kBlock / 64; ++w) {
-        const int k = wave_kernel((hw >> (8 * w)) & 0xFFu, S);
-        any = any || k == R || k == FL_ANY;
-      }
-      blk = any;  // block-uniform
-      mine = wk == R || wk == FL_ANY;
+    for (uint32_t w = 0; w < kBlock / 64; ++w) {
+      const int k = wave_kernel((hw >> (8 * w)) & 0xFFu, S);
+      any = any || k == R || k == FL_ANY;
     }
-    if (blk) fast_wave<S, R, RM>(kp, i, wave, hint, wk, mine, bail_list, counters, list_cap);
+    blk = any;  // block-uniform
+    mine = wk == R || wk == FL_ANY;
   }
+  if (blk) fast_wave<S, R, RM>(kp, i, wave, hint, wk, mine, bail_list, counters, list_cap);
 }
 
-// Both role instances of a split pass in one launch (GR_ROLES_MERGED=1, A/B):
-// workgroups [0, half) are the follower instance, [half, 2 half) the leader
-// instance. The two never touch the same lane (FastLane `take`), so they may
-// run side by side; the register allocation is the larger of the two.
+// Both role instances of a split pass in one launch: workgroups [0, half) are
+// the follower instance, [half, 2 half) the leader instance. The two never
+// touch the same lane (FastLane `take`), so they may run side by side; the
+// register allocation is the larger of the two (DESIGN.md 3 has the A/B against
+// two launches).
 template <int S, int RM>
-__global__ __launch_bounds__(kBlock, GR_LISTED_MIN_WAVES) void gr_roles_kernel(StepParams kp, uint32_t* bail_list,
-                                                                                uint32_t* counters, uint32_t list_cap) {
+__global__ __launch_bounds__(kBlock, 1) void gr_roles_kernel(StepParams kp, uint32_t* bail_list, uint32_t* counters,
+                                                             uint32_t list_cap) {
   const uint32_t half = gridDim.x / 2;
   if (blockIdx.x < half) roles_listed<S, FL_FOLLOWER, RM>(kp, bail_list, counters, list_cap, blockIdx.x, half);
   else roles_listed<S, FL_LEADER, RM>(kp, bail_list, counters, list_cap, blockIdx.x - half, half);
@@ -518,19 +459,20 @@ __global__ __launch_bounds__(kBlock, GR_LISTED_MIN_WAVES) void gr_roles_kernel(S
 // their register budget is their own (46 VGPRs for the leader's closed form;
 // with FastLane in the same kernel the allocation rose to FastLane's and
 // beyond): the waves whose hint says they were steady. A lane whose
-// preconditions fail stores nothing and is queued for FastLane (lists 24..31).
-// LC: unhinted waves' lanes try their own role's closed form (lane_closed_form),
-// the instance a pass runs when role instances follow it (TailPlan: the last
-// pass left lanes to them); a pass without them runs LC = false, whose code is
-// the steady state's alone (the headline measured 2-4 % slower with the branch
-// compiled in, though its waves never take it).
+// preconditions fail stores nothing and is queued for FastLane (the retry lists,
+// 32..39).
+// LC: role instances follow this kernel (tail_roles: the last pass left lanes to
+// them), and unhinted waves' lanes try their own role's closed form
+// (lane_closed_form) first. A pass without role instances runs LC = false, whose
+// code is the steady state's alone (the headline measured 2-4 % slower with the
+// branch compiled in, though its waves never take it); what it does not finish
+// the general kernel takes from the retry lists (GM_RETRY).
 template <int S, int RM, bool LC>
-__global__ __launch_bounds__(kBlock, GR_FAST_MIN_WAVES) void gr_steady_kernel(StepParams kp, uint32_t* bail_list,
-                                                                               uint32_t* counters, uint32_t list_cap,
-                                                                               const uint32_t* prev_counters) {
+__global__ __launch_bounds__(kBlock, 1) void gr_steady_kernel(StepParams kp, uint32_t* bail_list, uint32_t* counters,
+                                                              uint32_t list_cap, const uint32_t* prev_counters) {
   const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
   if (kp.tail_hint && i == 0) {
-    // the tail hint (TailPlan) from the previous pass's final counts (the other
+    // the tail hint (tail_roles) from the previous pass's final counts (the other
     // counter set: this pass's general kernel zeroes it after this kernel), so
     // the write to host memory is issued at the start of the pass, not at the
     // end of its last kernel, where the kernel's completion would wait for it
@@ -539,8 +481,7 @@ __global__ __launch_bounds__(kBlock, GR_FAST_MIN_WAVES) void gr_steady_kernel(St
     for (uint32_t l = 0; l < 8; ++l) nretry += prev_counters[(kRetryList0 + l) * kCounterStride];
 #pragma unroll
     for (uint32_t l = 0; l < kGeneralLists; ++l) na += prev_counters[l * kCounterStride];
-    const uint32_t roles = prev_counters[kListedWord] || nretry;
-    *(volatile uint32_t*)kp.tail_hint = (roles ? 1u : 0u) | ((na < (1u << 30) ? na : (1u << 30)) << 1);
+    *(volatile uint32_t*)kp.tail_hint = (nretry ? 1u : 0u) | ((na < (1u << 30) ? na : (1u << 30)) << 1);
   }
   const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane(i >> 6);
   const uint32_t hw = sload_u32(kp.hints + (uint64_t)blockIdx.x * (kBlock / 64));
@@ -550,7 +491,7 @@ __global__ __launch_bounds__(kBlock, GR_FAST_MIN_WAVES) void gr_steady_kernel(St
   if (!steady_hint<S>(hint)) {
     // not a steady wave: quiesced lanes finish here (QuiescedTick in closed
     // form), lanes with ticks or a ReadIndex go straight to the tick lists, and
-    // the rest are listed for the role instances (wave flag + lane mask)
+    // the rest to the retry lists
     const bool active = i < kp.n_lanes;
     uint64_t stage[kTickStageWords] = {};
     const int q = active ? quiet_step<S, RM>(kp, i, i, stage, kp.tick_stage != nullptr) : QS_DONE;
@@ -567,46 +508,27 @@ __global__ __launch_bounds__(kBlock, GR_FAST_MIN_WAVES) void gr_steady_kernel(St
     if constexpr (LC) {
       // the rest try the closed form of their own role (lane_closed_form); what
       // it leaves goes to the retry lists, which the role instances walk as
-      // dense waves (or, with no role instances after this kernel, the general
-      // kernel), instead of listing the whole wave
+      // dense waves
       LaneStats ls;
       uint32_t role = 0, myhint = 0;
       const bool fin = q == QS_OTHER && lane_closed_form<S, RM>(kp, i, i, &ls, &role, &myhint);
       if (fin) GR_CHECK_STATE(kp.st, i);
-      if ((threadIdx.x & 63) == 0) wave_flags(bail_list, list_cap)[wave] = 0;
       // the next pass's hint, as a hinted wave's: the lanes finished here agree
       // on it, the quiesced ones and those the closed form left are wildcards
       // (the latter go on to FastLane either way); a lane with ticks or a
       // ReadIndex blocks it (its wave stays on quiet_step's path)
       const bool tk = q == QS_TICK;
-      wave_finish<S>(kp, i, wave, true, active, tk, false, role, myhint, ls, bail_list, counters, list_cap);
+      wave_finish<S>(kp, i, wave, true, active, tk, false, myhint, ls, bail_list, counters, list_cap);
       if (!__ballot(active && !tk) && (threadIdx.x & 63) == 0) kp.hints_out[wave] = 0;
       bail_append(q == QS_OTHER && !fin, kRetryList0 + blockIdx.x % 8, bail_list, counters, list_cap, i);
-      return;
-    }
-    if (kp.no_roles) {
-      // no role instances follow (TailPlan): the rest go straight to the retry
-      // lists, which the general kernel then walks with its own
+    } else {
+      // no role instances follow: the rest go straight to the retry lists, which
+      // the general kernel then walks with its own
       bail_append(q == QS_OTHER, kRetryList0 + blockIdx.x % 8, bail_list, counters, list_cap, i);
-      if ((threadIdx.x & 63) == 0) {
-        wave_flags(bail_list, list_cap)[wave] = 0;
-        kp.hints_out[wave] = 0;
-      }
-      return;
-    }
-    const uint64_t rem = __ballot(q == QS_OTHER);
-    if ((threadIdx.x & 63) == 0) {
-      wave_flags(bail_list, list_cap)[wave] = (uint8_t)(rem ? (WF_LISTED | hint) : 0u);
-      if (rem) {
-        wave_masks(bail_list, list_cap)[wave] = rem;
-        counters[kListedWord] = 1u;  // the role instances have work (idempotent store)
-      } else {
-        kp.hints_out[wave] = 0;  // nothing here to speculate on next pass
-      }
+      if ((threadIdx.x & 63) == 0) kp.hints_out[wave] = 0;
     }
     return;
   }
-  if ((threadIdx.x & 63) == 0) wave_flags(bail_list, list_cap)[wave] = 0;
   LaneStats ls;
   bool done = false;
   uint32_t myhint = 0;
@@ -619,9 +541,8 @@ __global__ __launch_bounds__(kBlock, GR_FAST_MIN_WAVES) void gr_steady_kernel(St
     if (steady_follower_hint(hint)) done = SteadyFollower<S, RM>(kp, i, i).step(&ls, hint, &myhint);
     if (done) GR_CHECK_STATE(kp.st, i);
   }
-  // lanes not finished here (nothing stored) go to FastLane in the role
-  // instances that follow (lists 24..31), not straight to the general kernel
-#if GR_STEADY_BIT_STATS
+  // lanes not finished here (nothing stored) go to the retry lists (32..39):
+  // FastLane in the role instances that follow, not straight to the general kernel
   if (kp.hints) {
     // wave_finish's hint for a wave that is all this kernel's: a lane the closed
     // form left (hint 0, on to FastLane) is a wildcard like an idle one
@@ -630,10 +551,6 @@ __global__ __launch_bounds__(kBlock, GR_FAST_MIN_WAVES) void gr_steady_kernel(St
     if ((threadIdx.x & 63) == 0 && act) kp.hints_out[wave] = (uint8_t)nh;
   }
   if (kp.stats) steady_stats(kp, ls, lead);
-#else
-  wave_finish<S>(kp, i, wave, true, active, false, false, lead ? (uint32_t)GR_LEADER : 0u, myhint, ls, bail_list,
-                 counters, list_cap);
-#endif
   bail_append(active && !done, kRetryList0 + blockIdx.x % 8, bail_list, counters, list_cap, i);
 }
 
@@ -641,12 +558,14 @@ __global__ __launch_bounds__(kBlock, GR_FAST_MIN_WAVES) void gr_steady_kernel(St
 // handed over with ticks or a ReadIndex (the tick lists), in a kernel of its own so
 // its register budget (and occupancy) is its own; what it cannot finish goes to
 // the general lists. Launched only when some lane may carry LW_OTHER.
-#ifndef GR_TICK_MIN_WAVES
-#define GR_TICK_MIN_WAVES 1
-#endif
+// One-wave workgroups (kTickWg): a config-3 pass hands ~50k lanes to this kernel,
+// 196 workgroups of 256 lanes would leave 60 of the 256 CUs idle (round 4 ran
+// 256-lane workgroups). The launch bounds stay the 256-lane ones the kernel was
+// tuned with.
+constexpr uint32_t kTickWg = 64;
 template <int S, int RM>
-__global__ __launch_bounds__(kBlock, GR_TICK_MIN_WAVES) void gr_tick_kernel(StepParams kp, uint32_t* bail_list,
-                                                                             uint32_t* counters, uint32_t list_cap) {
+__global__ __launch_bounds__(kBlock, 1) void gr_tick_kernel(StepParams kp, uint32_t* bail_list, uint32_t* counters,
+                                                            uint32_t list_cap) {
   // the lists' exclusive prefix (one wave scans the kTickLists counters)
   __shared__ uint32_t tstart[kTickLists + 1];
   if (threadIdx.x < kTickLists) {
@@ -665,8 +584,6 @@ __global__ __launch_bounds__(kBlock, GR_TICK_MIN_WAVES) void gr_tick_kernel(Step
   // list entries: a wave may hold lanes of several replica blocks, so no
   // wave-uniform replica block for the routes (roles_listed)
   kp.route_wu = 0;
-  // one-wave workgroups by default (tick_wg): a config-3 pass hands ~50k lanes to
-  // this kernel, 196 workgroups of 256 lanes would leave 60 of the 256 CUs idle
   const uint32_t bw = blockDim.x;
   if (blockIdx.x * bw >= n) return;
   const uint32_t* tl = bail_list + tick_off(list_cap);
@@ -700,21 +617,14 @@ __global__ __launch_bounds__(kBlock, GR_TICK_MIN_WAVES) void gr_tick_kernel(Step
       }
       if (fin) {
         GR_CHECK_STATE(kp.st, p);
-        acc.leader_commit += ls.leader_commit;
-        acc.follower_commit += ls.follower_commit;
-        acc.escalated += ls.escalated;
-        acc.msgs_in += ls.msgs_in;
-        acc.msgs_out += ls.msgs_out;
-        acc.leader_in += ls.leader_in;
-        acc.leader_out += ls.leader_out;
-        acc.entries += ls.entries;
+        stats_add(acc, ls);
         acc.bailed += 1;
       } else {
         hand = true;  // the general lane steps it
       }
     }
-    general_append<S>(kp, hand, false, i, hand && kp.has_lane_peer ? kp.ln.u32(LR_LANE_PEER)[i] : i, blockIdx.x,
-                      bail_list, counters, list_cap);
+    general_append<S>(kp, hand, i, hand && kp.has_lane_peer ? kp.ln.u32(LR_LANE_PEER)[i] : i, blockIdx.x, bail_list,
+                      counters, list_cap);
   }
   if (kp.wclock && bw == 64) {  // profiling: the wave's span and its first entries' phases (second region)
     const uint64_t anyp = __ballot(tph[0] != 0);
@@ -792,17 +702,6 @@ __device__ inline void walk_chunks(const ListRange<NL>& r, uint32_t* counters, u
   }
 }
 
-__device__ inline __attribute__((always_inline)) void stats_add(LaneStats& acc, const LaneStats& ls) {
-  acc.leader_commit += ls.leader_commit;
-  acc.follower_commit += ls.follower_commit;
-  acc.escalated += ls.escalated;
-  acc.msgs_in += ls.msgs_in;
-  acc.msgs_out += ls.msgs_out;
-  acc.leader_in += ls.leader_in;
-  acc.leader_out += ls.leader_out;
-  acc.entries += ls.entries;
-}
-
 // Pass 2b: the general lane (every handler, escalation with prefix re-run)
 // over the handed-over lanes, in 64-lane chunks of the concatenated lists; also
 // clears the counters the next pass's kernels will use.
@@ -816,8 +715,7 @@ __global__ __launch_bounds__(kBlock, GR_GENERAL_MIN_WAVES) void gr_step_kernel(S
   ListRange<kBailLists> rl;
   rl.init(counters, 0, bail_list, list_cap, (mode & GM_RETRY) ? kBailLists : kGeneralLists);
   if (blockIdx.x == 0 && threadIdx.x < kCounters) next_counters[threadIdx.x * kCounterStride] = 0;
-  if (blockIdx.x == 0 && threadIdx.x == kCounters) next_counters[kListedWord] = 0;
-  if (blockIdx.x == 0 && threadIdx.x == kCounters + 1) next_counters[kGeneralNext] = 0;
+  if (blockIdx.x == 0 && threadIdx.x == kCounters) next_counters[kGeneralNext] = 0;
   LaneStats acc;
   // the general lane's message prefetch (gr_lane.h Lane::prefetch): one region
   // per wave (S <= 3: 30 KB; 120 KB for the workgroup's four waves)
@@ -880,16 +778,8 @@ __global__ __launch_bounds__(kBlock, GR_GENERAL_MIN_WAVES) void gr_step_kernel(S
 // The general kernel's grid: one 256-lane workgroup per CU fills the chip at its
 // occupancy (256 VGPRs + ~220 AGPRs: 1 wave per SIMD); never more than the stats
 // block has rows for. Kept small because with no bailed lanes the launch is pure
-// overhead. GR_GENERAL_BLOCKS overrides it (A/B runs).
+// overhead. GR_GENERAL_BLOCKS overrides it (general_blocks, below).
 constexpr uint32_t kGeneralBlocks = 256;
-inline uint32_t general_blocks() {
-  static const uint32_t v = [] {
-    const char* e = getenv("GR_GENERAL_BLOCKS");
-    const long x = e ? strtol(e, nullptr, 10) : 0;
-    return x > 0 ? (uint32_t)x : kGeneralBlocks;
-  }();
-  return v;
-}
 
 // Small passes (at most StepParams::small_blocks workgroups, 64k lanes by default) are
 // launch-bound: a 10k x 3 pass spent ~7 us in an empty general-kernel launch
@@ -905,20 +795,19 @@ __global__ __launch_bounds__(kBlock, 1) void gr_small_kernel(StepParams kp, uint
   const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
   const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane(i >> 6);
   if (blockIdx.x == 0 && threadIdx.x < kCounters) next_counters[threadIdx.x * kCounterStride] = 0;
-  if (blockIdx.x == 0 && threadIdx.x == kCounters) next_counters[kListedWord] = 0;
-  if (blockIdx.x == 0 && threadIdx.x == kCounters + 1) next_counters[kGeneralNext] = 0;
+  if (blockIdx.x == 0 && threadIdx.x == kCounters) next_counters[kGeneralNext] = 0;
   const uint32_t hw = kp.hints ? sload_u32(kp.hints + (uint64_t)blockIdx.x * (kBlock / 64)) : 0u;
   const uint32_t hint = (hw >> (8 * (wave & 3))) & 0xFFu;
   const int wk = wave_kernel(hint, S);
   LaneStats ls;
   bool bail = false;
-  uint32_t role = 0, myhint = 0, p = 0;
+  uint32_t myhint = 0, p = 0;
   const bool active = i < kp.n_lanes;
   if (active) {
     p = kp.has_lane_peer ? kp.ln.u32(LR_LANE_PEER)[i] : i;
-    if (wk == FL_FOLLOWER) bail = !fast_step<S, FL_FOLLOWER, RM_ANY>(kp, i, p, &ls, &role, hint, &myhint);
-    else if (wk == FL_LEADER) bail = !fast_step<S, FL_LEADER, RM_ANY>(kp, i, p, &ls, &role, hint, &myhint);
-    else bail = !fast_step<S, FL_ANY, RM_ANY>(kp, i, p, &ls, &role, hint, &myhint);
+    if (wk == FL_FOLLOWER) bail = !fast_step<S, FL_FOLLOWER, RM_ANY>(kp, i, p, &ls, nullptr, hint, &myhint);
+    else if (wk == FL_LEADER) bail = !fast_step<S, FL_LEADER, RM_ANY>(kp, i, p, &ls, nullptr, hint, &myhint);
+    else bail = !fast_step<S, FL_ANY, RM_ANY>(kp, i, p, &ls, nullptr, hint, &myhint);
     if (!bail) GR_CHECK_STATE(kp.st, p);
   }
   if (kp.hints) {  // the wave's next hint, as wave_finish writes it
@@ -1061,15 +950,14 @@ struct PassTiming {
   hipEvent_t ev[3];
 };
 
-
-// The tail plan: which optional launches a pass makes after its lean kernels.
-// Every tail launch but the general kernel's is optional for correctness: the
-// general lane handles any lane (the lanes no role instance steps reach it
-// through the retry lists, GM_RETRY). So the host decides from the last pass the device has reported
+// The tail plan: whether a split pass launches the role instances after its
+// steady kernel. They are optional for correctness: the general lane handles any
+// lane (the lanes no role instance steps reach it through the retry lists,
+// GM_RETRY). So the host decides from the last pass the device has reported
 // (StepParams::tail_hint, written by the steady kernel of each split pass from
 // the previous pass's counts into host-visible memory, read here without
-// synchronising: one or more passes back). In the steady state nothing is
-// listed: the pass is the steady kernel and one empty general launch. A launch
+// synchronising: one or more passes back). In the steady state the retry lists
+// are empty: the pass is the steady kernel and one empty general launch. A launch
 // with nothing to do costs its workgroups' dispatch (round-5 A/B, 1M x 3: steady
 // kernel alone 0.0622 ms per pass, with the round-4 tail of role instances +
 // general kernel 0.0671).
@@ -1086,68 +974,52 @@ constexpr uint32_t kTailAll = 0xFFFFFFFFu;  // no report yet: every launch
 inline uint32_t tail_word(const StepParams& kp) {
   return kp.tail_hint ? __atomic_load_n(kp.tail_hint, __ATOMIC_RELAXED) : kTailAll;
 }
-struct TailPlan {
-  bool roles;
-};
-inline TailPlan tail_plan(const StepParams& kp) {
-  const uint32_t th = tail_word(kp);
-  switch (kp.tail_mode) {
-    case 1:
-    case 3: return {true};
-    case 2: return {false};
-    default: return {(th & 1u) != 0};
-  }
+// Whether a split pass launches the role instances: StepParams::tail_mode 1 =
+// always, 2 = never, else from the tail hint.
+inline bool tail_roles(const StepParams& kp) {
+  if (kp.tail_mode == 1 || kp.tail_mode == 2) return kp.tail_mode == 1;
+  return (tail_word(kp) & 1u) != 0;
 }
 // The tick kernel's grid: its lanes are at most the active share of a pass
-// (kTickBlocks x 256 lanes in flight, in workgroups of tick_wg() lanes).
+// (kTickBlocks x 256 lanes in flight, in workgroups of kTickWg lanes).
 constexpr uint32_t kTickBlocks = 1024;
-inline uint32_t tick_wg() {  // GR_TICK_WG=256 (A/B runs): round 4's 256-lane workgroups
-  static const uint32_t v = [] {
-    const char* e = getenv("GR_TICK_WG");
-    const long x = e ? strtol(e, nullptr, 10) : 0;
-    return (x == 64 || x == 128 || x == 256) ? (uint32_t)x : 64u;
-  }();
-  return v;
-}
 
-// The role instances' grid when they scan the wave flags: enough waves to fill
-// the chip at their occupancy; with no listed wave each wave reads its flags
-// (one 64-byte load per 64 waves) and leaves.
+// Each half of the role instances' grid (gr_roles_kernel): enough waves to fill
+// the chip at their occupancy. With empty retry lists the launch costs about its
+// waves' dispatch, ~4 us at 1024 workgroups.
 constexpr uint32_t kRoleBlocks = 1024;
-// GR_ROLE_BLOCKS overrides it (A/B runs: an empty launch of the role instances
-// costs about its waves' dispatch, ~4 us at 1024 workgroups)
-inline uint32_t role_blocks() {
-  static const uint32_t v = [] {
-    const char* e = getenv("GR_ROLE_BLOCKS");
-    const long x = e ? strtol(e, nullptr, 10) : 0;
-    return x > 0 ? (uint32_t)x : kRoleBlocks;
-  }();
-  return v;
-}
-// Both role instances in one launch (gr_roles_kernel: the first half of the grid
-// the follower instance, the second the leader instance), so they run side by
-// side instead of one after the other: config 5 245.7 vs 256.6 us per pass, the
-// headline 0.0664 vs 0.0669 ms, config 3 64.9 vs 65.3 us (one A/B call, round 4).
-// GR_ROLES_MERGED=0 launches them in sequence (A/B runs).
-inline bool roles_merged() {
-  static const bool v = [] {
-    const char* e = getenv("GR_ROLES_MERGED");
-    return !(e && e[0] == '0');
-  }();
-  return v;
-}
 
-// Measurement knobs (A/B runs only; never set in tests or the bench):
-// GR_STEADY_LDS=<bytes> gives each steady-kernel workgroup that much dynamic LDS,
-// which caps its workgroups per CU (occupancy) without changing its code;
-// GR_SKIP_TAIL=<n> launches the steady kernel alone from the engine's n-th
-// launch on (no role instances, tick or general kernel, counters never cleared):
-// correct only while nothing is listed or handed over, i.e. the floor of a
-// steady-state pass after warm-up.
+// Every environment variable the engine library (gr_engine.hip and this
+// header) reads, and who sets it; the wire codec, a library of its own, reads
+// GRW_SEG_SHIFT (gr_wire.hip). All but GR_PHASES and the last three are read
+// once, at gr_create (gr_engine.hip).
+//   tests:   GR_SPLIT_MIN_LANES=<lanes> (StepParams::split from that many lanes),
+//            GR_SMALL_BLOCKS=<workgroups> (the fused small pass up to that many; 0:
+//            never), GR_TAIL_MODE=0|1|2 (StepParams::tail_mode)
+//   product: GR_ELECTIONS=1 (elections on the device), GR_QUIESCE_ON_DEVICE=1 (the
+//            quiesce manager on the device); dragonboat_amd/engine.py documents both
+//   tools:   GR_WAVE_CLOCK=<path> (per-wave spans of the general and tick kernels:
+//            tools/wave_clock.py, tools/tick_clock.py), GR_PHASES=1 (host-side
+//            phase times of a boundary pass on stderr)
+//   measurements of the open tail-launch and occupancy items (host-side effect
+//   only; never set in tests or the bench), read here on first use:
+//            GR_GENERAL_BLOCKS=<n>: the general kernel's grid instead of
+//            kGeneralBlocks.
+//            GR_STEADY_LDS=<bytes>: that much dynamic LDS per steady-kernel
+//            workgroup, which caps its workgroups per CU (occupancy) without
+//            changing its code.
+//            GR_SKIP_TAIL=<n>: the steady kernel alone from the engine's n-th launch
+//            on (no role instances, tick or general kernel, counters never
+//            cleared): correct only while nothing is handed over, i.e. the floor
+//            of a steady-state pass after warm-up.
 inline uint32_t env_u32(const char* name) {
   const char* e = getenv(name);
   const long x = e ? strtol(e, nullptr, 10) : 0;
   return x > 0 ? (uint32_t)x : 0u;
+}
+inline uint32_t general_blocks() {
+  static const uint32_t v = env_u32("GR_GENERAL_BLOCKS");
+  return v ? v : kGeneralBlocks;
 }
 inline uint32_t steady_lds() {
   static const uint32_t v = env_u32("GR_STEADY_LDS");
@@ -1158,55 +1030,35 @@ inline uint32_t skip_tail_from() {
   return v;
 }
 
-// *retry_left: the steady kernel ran without role instances after it (no_roles:
-// the lanes it did not finish are in the retry lists, GM_RETRY).
+// The lean kernels of a pass too large for the fused one. steady: the pass runs
+// the steady kernel; roles: and the role instances after it (tail_roles).
 template <int S, int RM>
-hipError_t launch_fast(const StepParams& kp0, uint32_t blocks, uint32_t* bail_list, uint32_t* cur, uint32_t* prev,
-                       uint32_t list_cap, hipStream_t s, bool skip_tail, bool roles, bool* retry_left) {
-  StepParams kp = kp0;
-  *retry_left = false;
-  if (kp.hints && kp.split) {  // a large pass: the role instances
-    // the steady kernel steps lane i = peer i with compile-time routes
-    if (RM != RM_ANY && !kp.has_lane_peer) {
-      // the steady lanes, then the role instances over the waves it listed and
-      // the lanes it left
-      kp.no_roles = roles ? 0 : 1;
-      if (roles && GR_LANE_CLOSED)
-        hipLaunchKernelGGL((gr_steady_kernel<S, RM, true>), dim3(blocks), dim3(kBlock), steady_lds(), s, kp, bail_list,
-                           cur, list_cap, (const uint32_t*)prev);
-      else
-        hipLaunchKernelGGL((gr_steady_kernel<S, RM, false>), dim3(blocks), dim3(kBlock), steady_lds(), s, kp, bail_list,
-                           cur, list_cap, (const uint32_t*)prev);
-      const hipError_t e0 = hipGetLastError();
-      if (e0 != hipSuccess || skip_tail) return e0;
-      if (!roles) {
-        *retry_left = true;
-        return hipSuccess;
-      }
-      const uint32_t rb = blocks < role_blocks() ? blocks : role_blocks();
-      if (roles_merged()) {
-        hipLaunchKernelGGL((gr_roles_kernel<S, RM>), dim3(2 * rb), dim3(kBlock), 0, s, kp, bail_list, cur, list_cap);
-        return hipGetLastError();
-      }
-      hipLaunchKernelGGL((gr_fast_kernel<S, FL_FOLLOWER, RM, true>), dim3(rb), dim3(kBlock), 0, s, kp, bail_list,
-                         cur, list_cap);
-      const hipError_t e1 = hipGetLastError();
-      if (e1 != hipSuccess) return e1;
-      hipLaunchKernelGGL((gr_fast_kernel<S, FL_LEADER, RM, true>), dim3(rb), dim3(kBlock), 0, s, kp, bail_list,
-                         cur, list_cap);
-    } else {
-      hipLaunchKernelGGL((gr_fast_kernel<S, FL_FOLLOWER, RM, false>), dim3(blocks), dim3(kBlock), 0, s, kp,
-                         bail_list, cur, list_cap);
-      const hipError_t err = hipGetLastError();
-      if (err != hipSuccess) return err;
-      hipLaunchKernelGGL((gr_fast_kernel<S, FL_LEADER, RM, false>), dim3(blocks), dim3(kBlock), 0, s, kp,
-                         bail_list, cur, list_cap);
-    }
+hipError_t launch_fast(const StepParams& kp, uint32_t blocks, uint32_t* bail_list, uint32_t* cur, uint32_t* prev,
+                       uint32_t list_cap, hipStream_t s, bool skip_tail, bool steady, bool roles) {
+  if (steady) {
+    // the steady lanes, then the role instances over the lanes it left
+    if (roles)
+      hipLaunchKernelGGL((gr_steady_kernel<S, RM, true>), dim3(blocks), dim3(kBlock), steady_lds(), s, kp, bail_list,
+                         cur, list_cap, (const uint32_t*)prev);
+    else
+      hipLaunchKernelGGL((gr_steady_kernel<S, RM, false>), dim3(blocks), dim3(kBlock), steady_lds(), s, kp, bail_list,
+                         cur, list_cap, (const uint32_t*)prev);
+    const hipError_t e0 = hipGetLastError();
+    if (e0 != hipSuccess || skip_tail || !roles) return e0;
+    const uint32_t rb = blocks < kRoleBlocks ? blocks : kRoleBlocks;
+    hipLaunchKernelGGL((gr_roles_kernel<S, RM>), dim3(2 * rb), dim3(kBlock), 0, s, kp, bail_list, cur, list_cap);
+  } else if (kp.hints && kp.split) {  // a large pass without the steady kernel: one launch per role
+    hipLaunchKernelGGL((gr_fast_kernel<S, FL_FOLLOWER, RM>), dim3(blocks), dim3(kBlock), 0, s, kp, bail_list, cur,
+                       list_cap);
+    const hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return err;
+    hipLaunchKernelGGL((gr_fast_kernel<S, FL_LEADER, RM>), dim3(blocks), dim3(kBlock), 0, s, kp, bail_list, cur,
+                       list_cap);
   } else {
     // a mid-size pass (more workgroups than a fused small pass, fewer lanes than
     // a split one): the route-generic instance (one fewer instance per route mode)
-    hipLaunchKernelGGL((gr_fast_kernel<S, FL_ANY, RM_ANY, false>), dim3(blocks), dim3(kBlock), 0, s, kp, bail_list,
-                       cur, list_cap);
+    hipLaunchKernelGGL((gr_fast_kernel<S, FL_ANY, RM_ANY>), dim3(blocks), dim3(kBlock), 0, s, kp, bail_list, cur,
+                       list_cap);
   }
   return hipGetLastError();
 }
@@ -1238,22 +1090,24 @@ hipError_t launch(const StepParams& kp_in, uint32_t* bail_list, uint32_t* counte
   // loopback instance also assumes one-chunk spaces
   const bool loop1 = kp.route_mode == RT_LOOPBACK && kp.in.n_chunks == 1 && kp.out.n_chunks == 1;
   const bool skip = skip_tail_from() && parity >= skip_tail_from();
-  const TailPlan plan = tail_plan(kp);
-  bool retry_left = false;
+  // a large pass of lanes i = peer i with compile-time routes: the steady kernel
+  const bool steady = kp.hints && kp.split && !kp.has_lane_peer && (loop1 || kp.route_mode == RT_AFFINE);
+  const bool roles = tail_roles(kp);
   StepParams kq = kp;
   if (parity < 2) kq.tail_hint = nullptr;  // the first passes' counts describe no steady state yet
   if (loop1)
-    err = launch_fast<S, RT_LOOPBACK>(kq, blocks, bail_list, cur, nxt, list_cap, s, skip, plan.roles, &retry_left);
+    err = launch_fast<S, RT_LOOPBACK>(kq, blocks, bail_list, cur, nxt, list_cap, s, skip, steady, roles);
   else if (kp.route_mode == RT_AFFINE)
-    err = launch_fast<S, RT_AFFINE>(kq, blocks, bail_list, cur, nxt, list_cap, s, skip, plan.roles, &retry_left);
+    err = launch_fast<S, RT_AFFINE>(kq, blocks, bail_list, cur, nxt, list_cap, s, skip, steady, roles);
   else
-    err = launch_fast<S, RM_ANY>(kq, blocks, bail_list, cur, nxt, list_cap, s, skip, plan.roles, &retry_left);
-  const uint32_t mode = retry_left ? GM_RETRY : 0u;
+    err = launch_fast<S, RM_ANY>(kq, blocks, bail_list, cur, nxt, list_cap, s, skip, steady, roles);
+  // the steady kernel ran and the role instances did not: its retry lanes are the general kernel's
+  const uint32_t mode = steady && !roles ? GM_RETRY : 0u;
   if (err != hipSuccess) return err;
   if (t && (err = hipEventRecord(t->ev[1], s)) != hipSuccess) return err;
   if (skip) return t ? hipEventRecord(t->ev[2], s) : hipSuccess;
   if (tick_lanes) {  // some lane may carry ticks or a ReadIndex (LW_OTHER)
-    const uint32_t tw = tick_wg(), tmax = kTickBlocks * (kBlock / tw);
+    const uint32_t tw = kTickWg, tmax = kTickBlocks * (kBlock / tw);
     const uint32_t tblocks = blocks * (kBlock / tw) < tmax ? blocks * (kBlock / tw) : tmax;
     // the route mode as the lean instances have it (compile-time routes: every
     // address of the lane's first round known before its first load)

@@ -619,7 +619,7 @@ struct StepParams {
   uint8_t has_locals;
   uint8_t has_lane_peer;
   uint8_t route_mode;
-  uint8_t split;       // follower-hinted waves go to the FL_FOLLOWER instance (gr_kernels.h)
+  uint8_t split;       // a large pass: the steady kernel and the role instances (gr_kernels.h launch_fast)
   uint8_t route_wu;    // route_g % 64 == 0: replica_of is wave-uniform
   // host-side launch choice (gr_kernels.h launch): passes of at most this many
   // workgroups run as one fused kernel (gr_small_kernel)
@@ -628,22 +628,18 @@ struct StepParams {
   // kWaveClockWords u64 (start and end clock, lanes, messages in, escalations,
   // leader messages), or nullptr
   uint64_t* wclock;
-  // lanes handed to the general kernel go to lists keyed by handler class
-  // (gr_kernels.h general_bin) instead of by role and workgroup
-  uint8_t bin_general;
   // the tail hint (gr_kernels.h kTailAll): one word of host-visible pinned
-  // memory the general kernel writes after each split pass (did the role
-  // instances have work, how many lanes the general kernel stepped), which the
-  // host reads, unsynchronised, to size the next launches' grids; nullptr: off
+  // memory the steady kernel of each split pass writes from the previous pass's
+  // final counts (bit 0: the retry lists held lanes, so the role instances had
+  // work; above it, how many lanes went to the general lists), which the host
+  // reads, unsynchronised, to decide whether the next pass launches the role
+  // instances; nullptr (the allocation failed): every launch, every pass
   uint32_t* tail_hint;
-  // which tail launches a pass makes (gr_kernels.h TailPlan): 0 = from the
-  // tail hint; 1 or 3 = the role instances always (round 4's schedule); 2 =
-  // never (the general kernel steps the listed waves and every hand-over).
-  // GR_TAIL_MODE at gr_create.
+  // whether a split pass launches the role instances (gr_kernels.h tail_roles):
+  // 0 = from the tail hint; 1 = always (round 4's schedule); 2 = never (the
+  // general kernel steps the retry lanes and every hand-over). GR_TAIL_MODE at
+  // gr_create.
   uint8_t tail_mode;
-  // set by the launcher for the steady kernel of a pass whose role instances do
-  // not run: its non-steady lanes go to the retry lists (gr_kernels.h GM_RETRY)
-  uint8_t no_roles;
   // the tick lane's staged inputs (TickStage): one record per tick-list entry,
   // written by the steady kernel (nullptr: the tick lane loads everything itself)
   uint64_t* tick_stage;

@@ -126,14 +126,14 @@ void run_lanes(const StepParams& kp) {
       done = q0 == QS_DONE;
       staged[i] = q0 == QS_TICK;
       g_steady_lanes += done;
-    } else if (split && q0 == QS_OTHER && !steady_hint<S>(hint) && GR_LANE_CLOSED &&
+    } else if (split && q0 == QS_OTHER && !steady_hint<S>(hint) &&
                (((i >> 6) + (g_hint_salt >> 4)) & 7u) != 3u && lane_closed_form<S, RM_ANY>(kp, i, p, &ls, &role_cf, &sh)) {
       // a pass with role instances runs the steady kernel's LC instance: the
       // closed form of an unhinted wave's lane's own role (gr_steady.h
       // lane_closed_form)
       done = true;
       g_steady_lanes++;
-    } else if (split && GR_LANE_CLOSED && (((i >> 6) + (g_hint_salt >> 4)) & 7u) != 3u) {
+    } else if (split && (((i >> 6) + (g_hint_salt >> 4)) & 7u) != 3u) {
       // what it leaves: the role instances' retry pass (FastLane without a hint, by role)
       bool skip = false;
       done = lean_step<S, FL_FOLLOWER>(kp, i, p, &ls, nullptr, 0u, nullptr, FL_FOLLOWER, &skip);
@@ -143,8 +143,8 @@ void run_lanes(const StepParams& kp) {
         if (skip) abort();
       }
     } else if (split && (((i >> 6) + (g_hint_salt >> 4)) & 7u) == 3u) {
-      // a lane of a pass whose role instances did not run (gr_kernels.h TailPlan,
-      // GM_RETRY): the steady kernel lists it for the general kernel
+      // a lane of a pass whose role instances did not run (gr_kernels.h tail_roles,
+      // GM_RETRY): the steady kernel leaves it to the general kernel
       listed.push_back(i);
       continue;
     } else if (fk == FL_LEADER) {

@@ -3,8 +3,8 @@ every pass (tests/devsim.DeviceLockstep: every peer, every mailbox, every
 result, every escalation). This is the schedule bench.py and
 tools/bench_configs.py time: gr_step_device over loopback spaces runs
 gr_steady_kernel (closed-form steady lanes, quiet_step, tick routing), the role
-instances over its wave lists (striding when the pass has more than 1,024
-workgroups), the tick kernel and the general kernel; gr_step (test_gpu.py's
+instances over its retry lists (a fixed grid, striding over the entries), the
+tick kernel and the general kernel; gr_step (test_gpu.py's
 Lockstep) never launches the steady kernel."""
 import numpy as np
 import pytest
@@ -70,10 +70,10 @@ def test_device_config5_full_size(gpu):
 
 @pytest.mark.parametrize("mode", ["1", "2"])
 def test_tail_modes_churn(gpu, monkeypatch, mode):
-    """The tail plan (gr_kernels.h TailPlan) forced each way on config-5 churn
+    """The tail plan (gr_kernels.h tail_roles) forced each way on config-5 churn
     over the split schedule (20k x 3, leader changes p = 0.1 every pass):
-    1 and 3 = the role instances every pass (round 4's schedule); 2 = never
-    (the general kernel steps the listed waves and the retry lanes itself).
+    1 = the role instances every pass (round 4's schedule); 2 = never (the
+    general kernel steps the retry lanes itself).
     Every peer, mailbox and result equals the oracle after every pass in each
     mode."""
     monkeypatch.setenv("GR_TAIL_MODE", mode)
@@ -90,6 +90,39 @@ def test_tail_modes_churn(gpu, monkeypatch, mode):
                 ch = P.inject_leader_change(cur, topo, 0.1, rng)
                 ls.inject(ch, cur[ch])
             ls.step(P.propose_locals(R * G, P.current_leaders(ls.export(), topo), pass_index=k))
+        assert ls.stats["injected"] > 0 and ls.stats["commits"] > 0
+    finally:
+        ls.close()
+
+
+@pytest.mark.parametrize("mode", ["1", "2"])
+def test_tail_modes_churn_whole_wave_blocks(gpu, monkeypatch, mode):
+    """test_tail_modes_churn with replica blocks of whole waves (20,032 x 3: 313
+    waves per block), the one layout in which the engine takes a wave's replica
+    block from its first lane (StepParams::route_wu). The retry lists and the
+    tick lists hold lanes of several replica blocks in one wave, so their
+    walkers (the role instances, the tick kernel) must take each lane's own
+    block. The population keeps both kinds of list non-empty (the ABI exposes no
+    list counts): leader changes with p = 0.1 from the second pass on leave
+    lanes the steady kernel does not finish (retry lists), and every third pass
+    gives every peer a Tick (tick lists). Every peer, mailbox and result equals
+    the oracle after every pass in each mode."""
+    monkeypatch.setenv("GR_TAIL_MODE", mode)
+    monkeypatch.setenv("GR_SPLIT_MIN_LANES", "1")
+    monkeypatch.setenv("GR_SMALL_BLOCKS", "0")
+    G, R = 20_032, 3
+    assert G % 64 == 0
+    topo = P.Topology(G, R)
+    rng = np.random.default_rng(60 + int(mode))
+    ls = devsim.DeviceLockstep(P.make_groups(G, R, seed=5), G, R)
+    try:
+        for k in range(8):
+            cur = ls.export()
+            if k >= 1:
+                ch = P.inject_leader_change(cur, topo, 0.1, rng)
+                ls.inject(ch, cur[ch])
+            ls.step(P.propose_locals(R * G, P.current_leaders(ls.export(), topo), pass_index=k,
+                                     ticks=1 if k % 3 == 2 else 0))
         assert ls.stats["injected"] > 0 and ls.stats["commits"] > 0
     finally:
         ls.close()

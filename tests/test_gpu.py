@@ -72,7 +72,7 @@ def test_split_pass_churn(gpu, mix, monkeypatch):
     """Large-pass schedule (StepParams::split) forced on a small population, with
     BASELINE config 5's leader changes every pass, checked against the oracle
     after every pass (state, every mailbox, results). mix = False: loopback
-    routes, so the steady kernel runs and the role instances walk its wave lists
+    routes, so the steady kernel runs and the role instances walk its retry lists
     while churn puts new leaders into follower-hinted waves; mix = True: peers
     group-major, so every wave holds both roles (unhinted waves through both
     instances, table routes)."""

@@ -29,11 +29,9 @@ def counters(d, kernel_sub):
 
 # The lean kernels of one headline pass (gr_kernels.h, a split pass over
 # loopback routes, RM = 3): the steady kernel, then the role instances over its
-# wave lists, in one launch (gr_roles_kernel, round 4) or as <S, 2> (followers)
-# and <S, 1> (leaders) with GR_ROLES_MERGED=0. A device pass's lean-kernel bytes
+# retry lists in one launch (gr_roles_kernel). A device pass's lean-kernel bytes
 # are the sum over the kernels it ran.
-ROLE_INSTANCES_MERGED = ("gr_steady_kernel<3, 3", "gr_roles_kernel<3, 3>")  # steady: <3, 3, LC>
-ROLE_INSTANCES_SPLIT = ("gr_steady_kernel<3, 3", "gr_fast_kernel<3, 2, 3, true>", "gr_fast_kernel<3, 1, 3, true>")
+ROLE_INSTANCES = ("gr_steady_kernel<3, 3", "gr_roles_kernel<3, 3>")  # steady: <3, 3, LC>
 
 
 def main(o):
@@ -69,8 +67,6 @@ def main(o):
             sq = counters(os.path.join(o, sub), kname)
             k.setdefault("sq", {}).update({c: sum(v[3:] or v) / len(v[3:] or v) for c, v in sq.items() if v})
         s["kernels"][kname] = k
-    merged = bool(counters(os.path.join(o, "fetch"), "gr_roles_kernel<3, 3>").get("FETCH_SIZE"))
-    ROLE_INSTANCES = ROLE_INSTANCES_MERGED if merged else ROLE_INSTANCES_SPLIT
     for kname in ROLE_INSTANCES:  # per instance, for the per-pass sum below
         f = counters(os.path.join(o, "fetch"), kname).get("FETCH_SIZE", [])
         w = counters(os.path.join(o, "write"), kname).get("WRITE_SIZE", [])
