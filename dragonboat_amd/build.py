@@ -110,10 +110,33 @@ def check_no_scratch(remarks, src):
                 raise RuntimeError(f"{os.path.basename(src)}: {name} uses {size} B/lane of scratch")
 
 
+# Kernels that must stay within a scalar-register count: a CU admits 256-lane
+# workgroups by their SGPRs too, floor(800 / (ceil(sgprs / 16) * 16 + 16)) of
+# them, so a steady-kernel instance above 80 runs 7 waves per SIMD, not 8, while
+# the compiler's occupancy remark still says 8 (gr_kernels.h kSteadySgprs).
+# TotalSGPRs of the remarks is the code object's .sgpr_count.
+STEADY_MAX_SGPRS = 80
+SGPR_BOUND_KERNELS = {"gr_steady_kernel": STEADY_MAX_SGPRS}
+
+
+def check_sgpr_bound(remarks, src):
+    """Parse the same remarks; raise if a kernel of SGPR_BOUND_KERNELS uses more SGPRs than its bound."""
+    name = None
+    for ln in remarks.splitlines():
+        if "Function Name:" in ln:
+            name = ln.split("Function Name:", 1)[1].split("[")[0].strip()
+        elif "TotalSGPRs" in ln and name:
+            n = int(ln.split(":")[-1].split("[")[0].strip())
+            for k, bound in SGPR_BOUND_KERNELS.items():
+                if k in name and n > bound:
+                    raise RuntimeError(f"{os.path.basename(src)}: {name} uses {n} SGPRs, above {bound}")
+
+
 def _hip_lib(out, srcs, deps, extra=(), force=False, scratch_check=True):
     """Compile every source to an object in parallel (hipcc, gfx950), then link `out`.
-    scratch_check: refuse lean-kernel instances that use scratch (product builds;
-    the coverage build's hit counters cost registers, and it is never timed)."""
+    scratch_check: refuse lean-kernel instances that use scratch, and steady
+    instances above their SGPR bound (product builds; the coverage build's hit
+    counters cost registers, and it is never timed)."""
     if not (force or _stale(out, deps, extra)):
         return out
     with _locked(out):
@@ -141,6 +164,7 @@ def _hip_lib_locked(out, srcs, deps, extra, scratch_check):
                 fh.write(r)
             if scratch_check:
                 check_no_scratch(r, s)
+                check_sgpr_bound(r, s)
     _run([HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", *objs, "-o", out])
     write_build_record(out, extra, digest, deps)
     return out

@@ -467,9 +467,16 @@ __global__ __launch_bounds__(kBlock, 1) void gr_roles_kernel(StepParams kp, uint
 // code is the steady state's alone (the headline measured 2-4 % slower with the
 // branch compiled in, though its waves never take it); what it does not finish
 // the general kernel takes from the retry lists (GM_RETRY).
+// The SGPR cap: a CU admits 256-lane workgroups by their scalar registers too,
+// floor(800 / (ceil(sgprs / 16) * 16 + 16)) of them, so 80 hold 8 waves per SIMD
+// and the 87-99 the instances took uncapped hold 7, whatever the compiler's
+// occupancy remark says (it counts VGPRs and LDS). Capped, the scalars that do
+// not fit live in lanes of a VGPR, not in memory (<3,3,false>: 9 of them, the
+// VGPR count unchanged at 56). build.py checks the bound (STEADY_MAX_SGPRS).
+constexpr int kSteadySgprs = 80;
 template <int S, int RM, bool LC>
-__global__ __launch_bounds__(kBlock, 1) void gr_steady_kernel(StepParams kp, uint32_t* bail_list, uint32_t* counters,
-                                                              uint32_t list_cap, const uint32_t* prev_counters) {
+__global__ __launch_bounds__(kBlock, 1) __attribute__((amdgpu_num_sgpr(kSteadySgprs))) void gr_steady_kernel(
+    StepParams kp, uint32_t* bail_list, uint32_t* counters, uint32_t list_cap, const uint32_t* prev_counters) {
   const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
   if (kp.tail_hint && i == 0) {
     // the tail hint (tail_roles) from the previous pass's final counts (the other
@@ -1035,19 +1042,25 @@ inline uint32_t skip_tail_from() {
 template <int S, int RM>
 hipError_t launch_fast(const StepParams& kp, uint32_t blocks, uint32_t* bail_list, uint32_t* cur, uint32_t* prev,
                        uint32_t list_cap, hipStream_t s, bool skip_tail, bool steady, bool roles) {
-  if (steady) {
-    // the steady lanes, then the role instances over the lanes it left
-    if (roles)
-      hipLaunchKernelGGL((gr_steady_kernel<S, RM, true>), dim3(blocks), dim3(kBlock), steady_lds(), s, kp, bail_list,
-                         cur, list_cap, (const uint32_t*)prev);
-    else
-      hipLaunchKernelGGL((gr_steady_kernel<S, RM, false>), dim3(blocks), dim3(kBlock), steady_lds(), s, kp, bail_list,
-                         cur, list_cap, (const uint32_t*)prev);
-    const hipError_t e0 = hipGetLastError();
-    if (e0 != hipSuccess || skip_tail || !roles) return e0;
-    const uint32_t rb = blocks < kRoleBlocks ? blocks : kRoleBlocks;
-    hipLaunchKernelGGL((gr_roles_kernel<S, RM>), dim3(2 * rb), dim3(kBlock), 0, s, kp, bail_list, cur, list_cap);
-  } else if (kp.hints && kp.split) {  // a large pass without the steady kernel: one launch per role
+  // launch() runs the steady kernel on compile-time routes only, so no
+  // route-generic instance of it (or of the role instances after it) is built
+  if constexpr (RM != RM_ANY) {
+    if (steady) {
+      // the steady lanes, then the role instances over the lanes it left
+      if (roles)
+        hipLaunchKernelGGL((gr_steady_kernel<S, RM, true>), dim3(blocks), dim3(kBlock), steady_lds(), s, kp, bail_list,
+                           cur, list_cap, (const uint32_t*)prev);
+      else
+        hipLaunchKernelGGL((gr_steady_kernel<S, RM, false>), dim3(blocks), dim3(kBlock), steady_lds(), s, kp, bail_list,
+                           cur, list_cap, (const uint32_t*)prev);
+      const hipError_t e0 = hipGetLastError();
+      if (e0 != hipSuccess || skip_tail || !roles) return e0;
+      const uint32_t rb = blocks < kRoleBlocks ? blocks : kRoleBlocks;
+      hipLaunchKernelGGL((gr_roles_kernel<S, RM>), dim3(2 * rb), dim3(kBlock), 0, s, kp, bail_list, cur, list_cap);
+      return hipGetLastError();
+    }
+  }
+  if (kp.hints && kp.split) {  // a large pass without the steady kernel: one launch per role
     hipLaunchKernelGGL((gr_fast_kernel<S, FL_FOLLOWER, RM>), dim3(blocks), dim3(kBlock), 0, s, kp, bail_list, cur,
                        list_cap);
     const hipError_t err = hipGetLastError();

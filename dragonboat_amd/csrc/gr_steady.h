@@ -432,12 +432,6 @@ GF_HD int quiet_step(const StepParams& kp, uint32_t i, uint32_t p, uint64_t* sta
 // every lane of it ran FastLane. The closed forms check every precondition, the
 // slot included, against the lane's state, so a lane that fails them has stored
 // nothing (false) and goes on to FastLane.
-// Read by nothing in this tree; was the build-time switch for this function
-// (A/B builds: 0). The previous revision's tests/native/hostlane.hip names it,
-// and every CPU parity test of that revision must still build against this
-// header, so the constant outlives its last use by one revision: delete it with
-// the next change here.
-#define GR_LANE_CLOSED 1
 template <int S, int RM>
 GF_HD bool lane_closed_form(const StepParams& kp, uint32_t i, uint32_t p, LaneStats* ls, uint32_t* role,
                             uint32_t* hint_out) {
