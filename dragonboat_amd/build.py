@@ -28,6 +28,7 @@ KAT_BIN = os.path.join(ROOT, "oracle", "_build", "kat_tests")
 HOSTLANE_LIB = os.path.join(ROOT, "tests", "_build", "libhostlane.so")
 HOSTLANE_ELECT_LIB = os.path.join(ROOT, "tests", "_build", "libhostlane_elect.so")
 QUIESCE_HOST_LIB = os.path.join(ROOT, "tests", "_build", "libquiesce_host.so")
+STEADY_WU_HOST_LIB = os.path.join(ROOT, "tests", "_build", "libsteady_wu_host.so")
 WIRE_SRC = os.path.join(ROOT, "dragonboat_amd", "csrc", "gr_wire.hip")
 WIRE_DEPS = [WIRE_SRC, os.path.join(ROOT, "include", "gpuraft_wire.h"), os.path.join(ROOT, "include", "gpuraft.h"),
              os.path.join(CSRC, "gr_scan.h")]
@@ -268,6 +269,22 @@ def build_quiesce_host(force=False):
     return QUIESCE_HOST_LIB
 
 
+def build_steady_wu_host(force=False):
+    """libsteady_wu_host.so: the steady kernel's wave-uniform addressing and its
+    predicate (gr_steady.h WaveAddr, gr_layout.h steady_wu_routes) compiled for
+    the host behind a C interface, for tests/test_steady_wu.py."""
+    os.makedirs(os.path.dirname(STEADY_WU_HOST_LIB), exist_ok=True)
+    src = os.path.join(ROOT, "tests", "native", "steady_wu_host.hip")
+    deps = ENGINE_DEPS + [src]
+    if not (force or _stale(STEADY_WU_HOST_LIB, deps)):
+        return STEADY_WU_HOST_LIB
+    with _locked(STEADY_WU_HOST_LIB):
+        if force or _stale(STEADY_WU_HOST_LIB, deps):
+            _run([HIPCC, "--cuda-host-only", "-O2", "-g", "-std=c++17", "-fPIC", "-shared",
+                  "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, src, "-o", STEADY_WU_HOST_LIB])
+    return STEADY_WU_HOST_LIB
+
+
 ORACLE_SAN_LIB = os.path.join(ROOT, "oracle", "_build", "liboracle_san.so")
 KAT_SAN_BIN = os.path.join(ROOT, "oracle", "_build", "kat_tests_san")
 HOSTLANE_SAN_LIB = os.path.join(ROOT, "tests", "_build", "libhostlane_san.so")
@@ -355,5 +372,6 @@ def build_all(force=False):
         build_wire_oracle(force)
         build_tools(force)
         build_quiesce_host(force)
+        build_steady_wu_host(force)
         for f in fs:
             f.result()

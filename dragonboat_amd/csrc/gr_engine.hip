@@ -100,6 +100,11 @@ struct gr_engine {
   uint8_t route_mode = RT_TABLE;  // of the bound routes (RT_TABLE, RT_AFFINE or RT_LOOPBACK)
   uint32_t route_g = 0, route_r = 0;
   uint32_t* route_base = nullptr;  // device [2][GR_SMAX][GR_SMAX]
+  // the steady kernel's wave-uniform addressing (gr_layout.h steady_wu_routes):
+  // whether the bound routes allow it, whether the spaces of the last
+  // gr_step_device pass did (steady_wu_space; true before the first), and
+  // GR_STEADY_WU=0 at gr_create (tests: the per-lane instance)
+  bool wu_routes = false, wu_spaces = true, wu_enabled = true;
   bool locals_set = false;
   bool locals_other = false;  // some bound local input has ticks / a ReadIndex / oversized counts (LW_OTHER)
   uint64_t passes = 0;
@@ -453,6 +458,7 @@ int gr_create(const gr_config* cfg, gr_engine** out) {
     const unsigned long v = strtoul(tm, nullptr, 10);
     if (v <= 2) e->tail_mode = (uint8_t)v;
   }
+  if (const char* wu = getenv("GR_STEADY_WU")) e->wu_enabled = !(wu[0] == '0' && wu[1] == 0);
   if (const char* el = getenv("GR_ELECTIONS")) e->elections = el[0] == '1';
   const char* qd = getenv("GR_QUIESCE_ON_DEVICE");
   if (const char* wc = getenv("GR_WAVE_CLOCK")) {
@@ -1661,6 +1667,12 @@ int gr_stats_reset(gr_engine* e) {
   return GR_OK;
 }
 
+int gr_steady_wave_uniform(gr_engine* e) {
+  if (!e) return GR_EINVAL;
+  std::lock_guard<std::mutex> guard(e->mu);
+  return e->routes_bound && e->wu_routes && e->wu_spaces && e->wu_enabled ? 1 : 0;
+}
+
 int gr_bind_routes(gr_engine* e, const uint32_t* in_pos, const uint32_t* out_pos, uint32_t n_peers) {
   if (!e || !in_pos || !out_pos || n_peers > e->cfg.max_peers) return GR_EINVAL;
   std::lock_guard<std::mutex> guard(e->mu);  // against a concurrent compact _begin/_end
@@ -1673,9 +1685,11 @@ int gr_bind_routes(gr_engine* e, const uint32_t* in_pos, const uint32_t* out_pos
     e->route_mode = is_loopback(base.data(), g, rr, e->S) ? RT_LOOPBACK : RT_AFFINE;
     e->route_g = g;
     e->route_r = rr;
+    e->wu_routes = steady_wu_routes(e->route_mode, e->S, g, rr, base.data());
   } else {
     e->route_mode = RT_TABLE;
     e->route_g = 0;
+    e->wu_routes = false;
   }
   for (uint32_t j = 0; j < e->S; ++j) {
     HIPCHK(hipMemcpy(e->ln.in_pos() + (size_t)j * e->cap, in_pos + (size_t)j * n_peers, (size_t)n_peers * 4,
@@ -1744,6 +1758,8 @@ static int step_device_locked(gr_engine* e, const void* in_space, void* out_spac
   kp.in = make_view(in_space, in_chunks, in_positions, depth);
   kp.out = make_view(out_space, out_chunks, out_positions, depth);
   kp.n_lanes = n_peers;
+  e->wu_spaces = steady_wu_space(kp.in) && steady_wu_space(kp.out);
+  kp.steady_wu = e->routes_bound && e->wu_routes && e->wu_spaces && e->wu_enabled ? 1 : 0;
   // lane = peer here, so a wave's hint carries over between passes
   const size_t hs = hint_stride(e->cap), hf = e->hint_flip++ & 1;
   kp.hints = e->hints + hf * hs;

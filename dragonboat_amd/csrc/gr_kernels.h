@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
+#include <type_traits>
 
 #include "gr_fast.h"
 #include "gr_steady.h"
@@ -471,10 +472,17 @@ __global__ __launch_bounds__(kBlock, 1) void gr_roles_kernel(StepParams kp, uint
 // floor(800 / (ceil(sgprs / 16) * 16 + 16)) of them, so 80 hold 8 waves per SIMD
 // and the 87-99 the instances took uncapped hold 7, whatever the compiler's
 // occupancy remark says (it counts VGPRs and LDS). Capped, the scalars that do
-// not fit live in lanes of a VGPR, not in memory (<3,3,false>: 9 of them, the
-// VGPR count unchanged at 56). build.py checks the bound (STEADY_MAX_SGPRS).
+// not fit live in lanes of a VGPR, not in memory (<3,3,false,false>: 11 of them
+// at 55 VGPRs; <3,3,false,true>: 12 at 49). build.py checks the bound
+// (STEADY_MAX_SGPRS).
+// WU: the hinted waves' closed forms address by wave (gr_steady.h WaveAddr: one
+// uniform base per region, 32-bit lane offsets, scalar route decisions) instead
+// of building a 64-bit address per lane and access; launch_fast takes it when
+// StepParams::steady_wu says the bound routes and spaces allow it. A template
+// parameter, not a run-time branch, for the reason LC is one.
 constexpr int kSteadySgprs = 80;
-template <int S, int RM, bool LC>
+static_assert(kBlock == (int)kTileW, "a workgroup's lanes are one state tile");
+template <int S, int RM, bool LC, bool WU>
 __global__ __launch_bounds__(kBlock, 1) __attribute__((amdgpu_num_sgpr(kSteadySgprs))) void gr_steady_kernel(
     StepParams kp, uint32_t* bail_list, uint32_t* counters, uint32_t list_cap, const uint32_t* prev_counters) {
   const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
@@ -541,11 +549,12 @@ __global__ __launch_bounds__(kBlock, 1) __attribute__((amdgpu_num_sgpr(kSteadySg
   uint32_t myhint = 0;
   const bool active = i < kp.n_lanes;
   const bool lead = S == 3 && steady_leader_hint(hint);  // wave-uniform: the wave's role is its hint's
+  using Addr = std::conditional_t<WU, WaveAddr<S, RM>, LaneAddr<S, RM>>;
   if (active) {
     if constexpr (S == 3) {
-      if (lead) done = SteadyLeader<S, RM>(kp, i, i).step(&ls, hint, &myhint);
+      if (lead) done = SteadyLeader<S, RM, Addr>(kp, i, i).step(&ls, hint, &myhint);
     }
-    if (steady_follower_hint(hint)) done = SteadyFollower<S, RM>(kp, i, i).step(&ls, hint, &myhint);
+    if (steady_follower_hint(hint)) done = SteadyFollower<S, RM, Addr>(kp, i, i).step(&ls, hint, &myhint);
     if (done) GR_CHECK_STATE(kp.st, i);
   }
   // lanes not finished here (nothing stored) go to the retry lists (32..39):
@@ -1002,7 +1011,8 @@ constexpr uint32_t kRoleBlocks = 1024;
 // once, at gr_create (gr_engine.hip).
 //   tests:   GR_SPLIT_MIN_LANES=<lanes> (StepParams::split from that many lanes),
 //            GR_SMALL_BLOCKS=<workgroups> (the fused small pass up to that many; 0:
-//            never), GR_TAIL_MODE=0|1|2 (StepParams::tail_mode)
+//            never), GR_TAIL_MODE=0|1|2 (StepParams::tail_mode), GR_STEADY_WU=0 (the
+//            steady kernel's per-lane addressing instance whatever the routes allow)
 //   product: GR_ELECTIONS=1 (elections on the device), GR_QUIESCE_ON_DEVICE=1 (the
 //            quiesce manager on the device); dragonboat_amd/engine.py documents both
 //   tools:   GR_WAVE_CLOCK=<path> (per-wave spans of the general and tick kernels:
@@ -1047,12 +1057,10 @@ hipError_t launch_fast(const StepParams& kp, uint32_t blocks, uint32_t* bail_lis
   if constexpr (RM != RM_ANY) {
     if (steady) {
       // the steady lanes, then the role instances over the lanes it left
-      if (roles)
-        hipLaunchKernelGGL((gr_steady_kernel<S, RM, true>), dim3(blocks), dim3(kBlock), steady_lds(), s, kp, bail_list,
-                           cur, list_cap, (const uint32_t*)prev);
-      else
-        hipLaunchKernelGGL((gr_steady_kernel<S, RM, false>), dim3(blocks), dim3(kBlock), steady_lds(), s, kp, bail_list,
-                           cur, list_cap, (const uint32_t*)prev);
+      auto* const k = roles ? (kp.steady_wu ? gr_steady_kernel<S, RM, true, true> : gr_steady_kernel<S, RM, true, false>)
+                            : (kp.steady_wu ? gr_steady_kernel<S, RM, false, true> : gr_steady_kernel<S, RM, false, false>);
+      hipLaunchKernelGGL(k, dim3(blocks), dim3(kBlock), steady_lds(), s, kp, bail_list, cur, list_cap,
+                         (const uint32_t*)prev);
       const hipError_t e0 = hipGetLastError();
       if (e0 != hipSuccess || skip_tail || !roles) return e0;
       const uint32_t rb = blocks < kRoleBlocks ? blocks : kRoleBlocks;

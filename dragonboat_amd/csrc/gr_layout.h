@@ -621,6 +621,9 @@ struct StepParams {
   uint8_t route_mode;
   uint8_t split;       // a large pass: the steady kernel and the role instances (gr_kernels.h launch_fast)
   uint8_t route_wu;    // route_g % 64 == 0: replica_of is wave-uniform
+  // host-side launch choice (gr_kernels.h launch_fast): the steady kernel's
+  // wave-uniform addressing instance (steady_wu_routes and steady_wu_space hold)
+  uint8_t steady_wu;
   // host-side launch choice (gr_kernels.h launch): passes of at most this many
   // workgroups run as one fused kernel (gr_small_kernel)
   uint32_t small_blocks;
@@ -699,11 +702,52 @@ constexpr int RM_ANY = -1;
 // The replica block of lane i (RT_LOOPBACK / RT_AFFINE: lane i = r * route_g + g).
 // StepParams::route_wu (route_g a multiple of 64): a wave's lanes share r, so it
 // is one scalar division per wave instead of a vector division per lane.
+// The wave's block is then found by a chain of at most NR - 1 scalar compares
+// (lane i is below NR * route_g; routes_of: NR = S, since gr_bind_routes binds at
+// most S replica blocks): the scalar unit has no division, and the compiler ran
+// the quotient of the first lane's index through the vector unit's
+// float-reciprocal sequence, ~20 vector instructions per wave for a value below S.
+template <int NR>
+__host__ __device__ inline uint32_t replica_chain(uint32_t i, uint32_t route_g) {
+  uint32_t r = 0, x = i;
+#pragma unroll
+  for (int k = 1; k < NR; ++k) {
+    const bool up = x >= route_g;
+    x -= up ? route_g : 0u;
+    r += up ? 1u : 0u;
+  }
+  return r;
+}
+template <int NR = 0>  // 0: no bound on the replica block known (division)
 __host__ __device__ inline uint32_t replica_of(const StepParams& kp, uint32_t i) {
 #if defined(__HIP_DEVICE_COMPILE__)
-  if (kp.route_wu) return __builtin_amdgcn_readfirstlane(i) / kp.route_g;
+  if (kp.route_wu) {
+    const uint32_t i0 = __builtin_amdgcn_readfirstlane(i);
+    if constexpr (NR > 0) return replica_chain<NR>(i0, kp.route_g);
+    return i0 / kp.route_g;
+  }
 #endif
   return i / kp.route_g;
+}
+// The replica-major routes (RT_LOOPBACK, RT_AFFINE) of lane i of replica block r.
+template <int S>
+__host__ __device__ inline void block_routes(const StepParams& kp, uint32_t mode, uint32_t i, uint32_t r, uint32_t* in,
+                                             uint32_t* out) {
+  const uint32_t g = i - r * kp.route_g;
+#pragma unroll
+  for (int j = 0; j < S; ++j) {
+    if (mode == RT_LOOPBACK) {
+      const bool none = (uint32_t)j == r || (uint32_t)j >= kp.route_r;
+      const uint32_t n = kp.route_r * kp.route_g;
+      in[j] = none ? NOPOS : j * n + i;
+      out[j] = none ? NOPOS : r * n + j * kp.route_g + g;
+    } else {
+      const uint32_t bi = kp.route_base[(0 * GR_SMAX + r) * GR_SMAX + j];
+      const uint32_t bo = kp.route_base[(1 * GR_SMAX + r) * GR_SMAX + j];
+      in[j] = bi == NOPOS ? NOPOS : bi + g;
+      out[j] = bo == NOPOS ? NOPOS : bo + g;
+    }
+  }
 }
 // Every route of lane i at once (in[j], out[j] for j < S): the lane's replica
 // block and group are divided out once, not once per slot and direction.
@@ -711,21 +755,7 @@ template <int S, int RM = RM_ANY>
 __host__ __device__ inline void routes_of(const StepParams& kp, uint32_t i, uint32_t* in, uint32_t* out) {
   const uint32_t mode = RM == RM_ANY ? (uint32_t)kp.route_mode : (uint32_t)RM;
   if (mode == RT_LOOPBACK || mode == RT_AFFINE) {
-    const uint32_t r = replica_of(kp, i), g = i - r * kp.route_g;
-#pragma unroll
-    for (int j = 0; j < S; ++j) {
-      if (mode == RT_LOOPBACK) {
-        const bool none = (uint32_t)j == r || (uint32_t)j >= kp.route_r;
-        const uint32_t n = kp.route_r * kp.route_g;
-        in[j] = none ? NOPOS : j * n + i;
-        out[j] = none ? NOPOS : r * n + j * kp.route_g + g;
-      } else {
-        const uint32_t bi = kp.route_base[(0 * GR_SMAX + r) * GR_SMAX + j];
-        const uint32_t bo = kp.route_base[(1 * GR_SMAX + r) * GR_SMAX + j];
-        in[j] = bi == NOPOS ? NOPOS : bi + g;
-        out[j] = bo == NOPOS ? NOPOS : bo + g;
-      }
-    }
+    block_routes<S>(kp, mode, i, replica_of<S>(kp, i), in, out);
     return;
   }
 #pragma unroll
@@ -749,6 +779,39 @@ __host__ __device__ inline uint32_t route_of(const StepParams& kp, uint32_t dir,
     return b == NOPOS ? NOPOS : b + g;
   }
   return j * kp.n_lanes + i;
+}
+
+// When the steady kernel may address by wave (gr_steady.h WaveAddr): a wave's 64
+// lanes are consecutive and 64-aligned in every region they touch, so the wave
+// lies in one state tile and each of its mailbox runs in one mailbox tile.
+// Lanes are peers (no lane-to-peer table: the steady kernel's own condition),
+// and the routes are replica-major with every block 64-aligned:
+//   RT_LOOPBACK: route_g and route_r * route_g multiples of 64 (in = j * n + i,
+//                out = r * n + j * route_g + g);
+//   RT_AFFINE:   route_g a multiple of 64 and every base that is not NOPOS too.
+// base: the bound tables' [2][GR_SMAX][GR_SMAX] block bases (RT_AFFINE only).
+constexpr uint32_t kWaveLanes = 64;
+static_assert(kTileW % kWaveLanes == 0, "a 64-aligned wave lies inside one tile");
+__host__ __device__ inline bool steady_wu_routes(uint32_t mode, uint32_t S, uint32_t route_g, uint32_t route_r,
+                                                 const uint32_t* base) {
+#if !GR_TILE || GR_PAIR
+  return false;  // WaveAddr is written for the tiled, unpaired rows
+#endif
+  if (route_g == 0 || route_g % kWaveLanes) return false;
+  if (mode == RT_LOOPBACK) return ((uint64_t)route_r * route_g) % kWaveLanes == 0;
+  if (mode != RT_AFFINE || !base) return false;
+  for (uint32_t d = 0; d < 2; ++d)
+    for (uint32_t r = 0; r < route_r && r < GR_SMAX; ++r)
+      for (uint32_t j = 0; j < S && j < GR_SMAX; ++j) {
+        const uint32_t b = base[(d * GR_SMAX + r) * GR_SMAX + j];
+        if (b != NOPOS && b % kWaveLanes) return false;
+      }
+  return true;
+}
+// ... and its mailbox offsets are 32 bits from the space's base: the hot region
+// (n_chunks hot chunks) must end at or below 4 GiB.
+__host__ __device__ inline bool steady_wu_space(const SpaceView& v) {
+  return (uint64_t)v.n_chunks * v.hot_bytes <= (1ull << 32);
 }
 
 }  // namespace gr

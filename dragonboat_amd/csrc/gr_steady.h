@@ -78,24 +78,173 @@ __host__ __device__ inline bool steady_hint(uint32_t h) {
 constexpr int kSteadyLeaderMsgBits = 3, kSteadyFollowerMsgBits = 2;
 static_assert(kUniformMax * 2 < (1u << kSteadyLeaderMsgBits), "a steady leader's msgs_out (S = 3) must fit");
 
-template <int RM>
-struct SteadyBase {
+// How a closed-form lane finds its state fields, mailboxes and lane rows: the
+// lanes below take one of two addressing policies, the same interface over
+//   LaneAddr: a 64-bit address per lane and access, from the lane's own routes
+//   (any route mode, any lane-to-peer table; the host builds; lane_closed_form);
+//   WaveAddr: a wave-uniform base per region and a 32-bit offset per lane.
+// s64(row): the peer's field; has_in / has_out(j), min / mout(j): slot j's
+// mailboxes (min(j) of a slot without one is position 0's, loaded and dropped);
+// in_of(slot, &has), has_out_of(slot): those of a slot known at run time (a
+// follower's leader); lword() ...: the lane rows.
+template <int S, int RM>
+struct LaneAddr {
   static constexpr bool kOneChunk = RM == RT_LOOPBACK;
+  using Box = Mailbox;
   const StepParams& kp;
   const uint32_t i, p;
-  GF_HD SteadyBase(const StepParams& k, uint32_t lane, uint32_t peer) : kp(k), i(lane), p(peer) {}
+  uint32_t gin[S], gout[S];
+  GF_HD LaneAddr(const StepParams& k, uint32_t lane, uint32_t peer) : kp(k), i(lane), p(peer) {
+    routes_of<S, RM>(kp, i, gin, gout);
+  }
   GF_HD uint64_t& s64(uint32_t row) const { return kp.st.u64(row)[p]; }
-  GF_HD Mailbox min_at(uint32_t g) const { return kp.in.template at<kOneChunk>(g); }
-  GF_HD Mailbox mout_at(uint32_t g) const { return kp.out.template at<kOneChunk>(g); }
+  GF_HD bool has_in(int j) const { return gin[j] != NOPOS; }
+  GF_HD bool has_out(int j) const { return gout[j] != NOPOS; }
+  GF_HD Box min(int j) const { return kp.in.template at<kOneChunk>(has_in(j) ? gin[j] : 0u); }
+  GF_HD Box mout(int j) const { return kp.out.template at<kOneChunk>(gout[j]); }
+  GF_HD Box in_of(uint32_t slot, bool* has) const {
+    uint32_t g = NOPOS;
+#pragma unroll
+    for (int j = 0; j < S; ++j) g = (uint32_t)j == slot ? gin[j] : g;
+    *has = g != NOPOS;
+    return kp.in.template at<kOneChunk>(g != NOPOS ? g : 0u);
+  }
+  GF_HD bool has_out_of(uint32_t slot) const {
+    uint32_t g = NOPOS;
+#pragma unroll
+    for (int j = 0; j < S; ++j) g = (uint32_t)j == slot ? gout[j] : g;
+    return g != NOPOS;
+  }
+  GF_HD uint32_t& lword() const { return kp.ln.u32(LR_LWORD)[i]; }
+  GF_HD uint8_t& rflags() const { return kp.ln.u8(LR_RFLAGS)[i]; }
+  GF_HD uint8_t& prop_result() const { return kp.ln.u8(LR_PROP_RESULT)[i]; }
+  GF_HD uint64_t& append_from() const { return kp.ln.u64(LR_APPEND_FROM)[i]; }
+};
+
+// A value the whole wave shares, as a scalar (device code; identity in host builds).
+GF_HD uint32_t wave_uniform(uint32_t v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
+#else
+  return v;
+#endif
+}
+
+// A wave-uniform offset as an opaque scalar (device code). Added to a lane
+// offset it makes one 32-bit value the compiler cannot take apart again: left
+// visible, a constant row offset above the instruction's immediate range was
+// split from the sum and added per lane, in 64 bits.
+GF_HD uint32_t scalar_offset(uint32_t v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm("" : "+s"(v));
+#endif
+  return v;
+}
+
+// A mailbox of a wave whose 64 positions are consecutive in one tile of the
+// space's hot region: the region's base (uniform), the tile's byte offset in it
+// and the first lane's position in the tile (scalars), and the lane. Every field
+// address is hot + (uint32_t)(scalar part + lane part): one 32-bit vector add,
+// formed as ONE value and added to the base once (a 64-bit sum of base, tile
+// offset and lane offset fell back to 64-bit vector adds per lane). The hot
+// fields only (Mailbox, gr_layout.h): what a uniform mailbox stores.
+struct WaveBox {
+  uint8_t* hot;
+  uint32_t tb, l0, lane;
+  template <class T>
+  GF_HD T& at(uint32_t field_off) const {  // the field array at field_off of the tile, elements of T
+    return *reinterpret_cast<T*>(hot + (uint32_t)((tb + field_off + (uint32_t)sizeof(T) * l0) + (uint32_t)sizeof(T) * lane));
+  }
+  GF_HD uint8_t& cnt() const { return at<uint8_t>(0); }
+  GF_HD uint32_t& mterm() const { return at<uint32_t>(kTileW); }
+  GF_HD uint32_t& t32(uint32_t k, uint32_t) const { return at<uint32_t>((kHotH + k * kHotK) * kTileW); }  // MT_CDELTA
+  GF_HD uint64_t& u64(uint32_t k, uint32_t) const { return at<uint64_t>((kHotH + k * kHotK + 4u) * kTileW); }  // MF_LOG_INDEX
+};
+
+// Wave-uniform addressing (gr_layout.h steady_wu_routes, steady_wu_space): the
+// wave's first lane i0 is a multiple of 64, lane = peer, so the wave lies in
+// state tile i0 / 256 and its mailbox runs start at the first lane's routes.
+// The scalars are the routes of lane i0 (the replica block from a compare
+// chain, replica_chain) and what follows from them; the lane contributes its index
+// in the wave, once. "No mailbox for this slot" is a scalar decision.
+template <int S, int RM>
+struct WaveAddr {
+  static_assert(RM == RT_LOOPBACK || RM == RT_AFFINE, "replica-major routes");
+  static_assert(GR_TILE && !GR_PAIR, "the tiled, unpaired rows (steady_wu_routes)");
+  static constexpr bool kOneChunk = RM == RT_LOOPBACK;
+  using Box = WaveBox;
+  const StepParams& kp;
+  const uint32_t i;
+  uint32_t i0, lane;
+  uint32_t gin[S], gout[S];  // of lane i0
+  GF_HD WaveAddr(const StepParams& k, uint32_t ln, uint32_t) : kp(k), i(ln) {
+    i0 = wave_uniform(ln) & ~(kWaveLanes - 1);
+    lane = ln & (kWaveLanes - 1);
+    block_routes<S>(kp, RM, i0, replica_chain<S>(i0, kp.route_g), gin, gout);
+#pragma unroll
+    for (int j = 0; j < S; ++j) {
+      gin[j] = wave_uniform(gin[j]);
+      gout[j] = wave_uniform(gout[j]);
+    }
+  }
+  GF_HD uint64_t& s64(uint32_t row) const {
+    uint8_t* tile = kp.st.base + (uint64_t)(i0 >> GR_TILE_SHIFT) * (8ull * kTileW * rows_u64(S));
+    return *reinterpret_cast<uint64_t*>(tile + (uint32_t)(scalar_offset(8u * (row * kTileW + (i0 & kTileM))) + 8u * lane));
+  }
+  GF_HD Box box(const SpaceView& v, uint32_t g0) const {
+    uint32_t c = 0;
+    if (!kOneChunk && v.n_chunks != 1) c = wave_uniform(g0 / v.pc);
+    const uint32_t local = g0 - c * v.pc;
+    Box b;
+    b.hot = v.base;
+    b.tb = c * (uint32_t)v.hot_bytes + (local >> GR_TILE_SHIFT) * (uint32_t)tile_hot_bytes(v.depth);
+    b.l0 = local & kTileM;
+    b.lane = lane;
+    return b;
+  }
+  GF_HD bool has_in(int j) const { return gin[j] != NOPOS; }
+  GF_HD bool has_out(int j) const { return gout[j] != NOPOS; }
+  GF_HD Box min(int j) const { return box(kp.in, has_in(j) ? gin[j] : 0u); }
+  GF_HD Box mout(int j) const { return box(kp.out, gout[j]); }
+  GF_HD Box in_of(uint32_t slot, bool* has) const {
+    uint32_t g = NOPOS;
+#pragma unroll
+    for (int j = 0; j < S; ++j) g = (uint32_t)j == slot ? gin[j] : g;
+    *has = g != NOPOS;
+    return box(kp.in, g != NOPOS ? g : 0u);
+  }
+  GF_HD bool has_out_of(uint32_t slot) const {
+    uint32_t g = NOPOS;
+#pragma unroll
+    for (int j = 0; j < S; ++j) g = (uint32_t)j == slot ? gout[j] : g;
+    return g != NOPOS;
+  }
+  template <class T>
+  GF_HD T& row(T* r) const {  // element i of a lane row: the wave's run from a uniform base
+    return *reinterpret_cast<T*>(reinterpret_cast<uint8_t*>(r + i0) + (uint32_t)sizeof(T) * lane);
+  }
+  GF_HD uint32_t& lword() const { return row(kp.ln.u32(LR_LWORD)); }
+  GF_HD uint8_t& rflags() const { return row(kp.ln.u8(LR_RFLAGS)); }
+  GF_HD uint8_t& prop_result() const { return row(kp.ln.u8(LR_PROP_RESULT)); }
+  GF_HD uint64_t& append_from() const { return row(kp.ln.u64(LR_APPEND_FROM)); }
+};
+
+template <class A>
+struct SteadyBase {
+  const A a;
+  const StepParams& kp;
+  GF_HD SteadyBase(const StepParams& k, uint32_t lane, uint32_t peer) : a(k, lane, peer), kp(k) {}
+  GF_HD uint64_t& s64(uint32_t row) const { return a.s64(row); }
   GF_HD static uint64_t umin(uint64_t a, uint64_t b) { return a < b ? a : b; }
   GF_HD static uint64_t umax(uint64_t a, uint64_t b) { return a < b ? b : a; }
 };
 
-template <int S, int RM>
-struct SteadyLeader : SteadyBase<RM> {
-  using B = SteadyBase<RM>;
+template <int S, int RM, class A = LaneAddr<S, RM>>
+struct SteadyLeader : SteadyBase<A> {
+  using B = SteadyBase<A>;
   using B::kp;
-  using B::i;
+  using B::a;
+  using Box = typename A::Box;
   using Rw = Rows<S>;
   static_assert(S == 3, "the closed form is the median of three voters");
   GF_HD SteadyLeader(const StepParams& k, uint32_t lane, uint32_t peer) : B(k, lane, peer) {}
@@ -103,19 +252,17 @@ struct SteadyLeader : SteadyBase<RM> {
   // true: the pass is done (state, messages, results stored); false: nothing stored.
   GF_HD bool step(LaneStats* ls, uint32_t hint, uint32_t* hint_out) {
     const uint32_t hself = (hint >> WH_SLOT_SHIFT) & 7u;  // wave-uniform
-    uint32_t gin[S], gout[S];
-    routes_of<S, RM>(kp, i, gin, gout);
     // ---- one load round
     const uint64_t hdr = ntld(B::s64(SR_HDR));
     const uint64_t term = ntld(B::s64(SR_TERM));
     const uint64_t hi0 = ntld(B::s64(SR_LAST_INDEX));
-    const uint32_t lw = kp.has_locals ? ntld(kp.ln.u32(LR_LWORD)[i]) : 0u;
+    const uint32_t lw = kp.has_locals ? ntld(a.lword()) : 0u;
     uint32_t cb[S], mt[S];
     uint64_t x[S][2], m[S];
 #pragma unroll
     for (int j = 0; j < S; ++j) {
-      const bool in = gin[j] != NOPOS;
-      const Mailbox mb = B::min_at(in ? gin[j] : 0u);
+      const bool in = a.has_in(j);
+      const Box mb = a.min(j);
       cb[j] = in ? (uint32_t)ntld(mb.cnt()) : 0u;
       mt[j] = in ? ntld(mb.mterm()) : 0u;
       x[j][0] = in ? ntld(mb.u64(0, MF_LOG_INDEX)) : 0ull;
@@ -126,8 +273,7 @@ struct SteadyLeader : SteadyBase<RM> {
 #pragma unroll
     for (int j = 0; j < S; ++j) {
       x[j][1] = x[j][0] + 1;
-      if (gin[j] != NOPOS && mb_n(cb[j]) >= 2 && !mb_shared(cb[j]))
-        x[j][1] = ntld(B::min_at(gin[j]).u64(1, MF_LOG_INDEX));
+      if (a.has_in(j) && mb_n(cb[j]) >= 2 && !mb_shared(cb[j])) x[j][1] = ntld(a.min(j).u64(1, MF_LOG_INDEX));
     }
     // committed follows from lastIndex and the header's lag field (H_CL); only a
     // lane whose field is clear loads the row, with that second round
@@ -181,7 +327,7 @@ struct SteadyLeader : SteadyBase<RM> {
     ok = ok && (ncb < 1 || commit_delta(bc0, hi0, &cd0)) && (ncb < 2 || commit_delta(bc1, hi0, &cd1)) &&
          (np == 0 || commit_delta(c, hi0, &cdp));
 #pragma unroll
-    for (int j = 0; j < S; ++j) ok = ok && ((uint32_t)j == hself || nout == 0 || gout[j] != NOPOS);
+    for (int j = 0; j < S; ++j) ok = ok && ((uint32_t)j == hself || nout == 0 || a.has_out(j));
     if (!ok) return false;
     // ---- stores
     const uint64_t hi = hi0 + np;  // the proposal's entry (no new run: the newest one is at term)
@@ -212,8 +358,8 @@ struct SteadyLeader : SteadyBase<RM> {
     const uint32_t nb = nout | MB_UNIFORM | (shared ? MB_SHARED : 0u) | (np ? 1u << (MB_N1_SHIFT + ncb) : 0u);
 #pragma unroll
     for (int j = 0; j < S; ++j) {
-      if (gout[j] == NOPOS) continue;
-      const Mailbox mb = B::mout_at(gout[j]);
+      if (!a.has_out(j)) continue;
+      const Box mb = a.mout(j);
       if ((uint32_t)j == hself || nout == 0) {
         ntst(mb.cnt(), (uint8_t)0);
         continue;
@@ -234,8 +380,8 @@ struct SteadyLeader : SteadyBase<RM> {
       ntst(mb.mterm(), (uint32_t)term);
       ntst(mb.cnt(), (uint8_t)nb);
     }
-    if (np) kp.ln.u8(LR_PROP_RESULT)[i] = (uint8_t)GR_PROP_APPENDED;
-    ntst(kp.ln.u8(LR_RFLAGS)[i], (uint8_t)(np ? RF_PROPOSE : 0));
+    if (np) a.prop_result() = (uint8_t)GR_PROP_APPENDED;
+    ntst(a.rflags(), (uint8_t)(np ? RF_PROPOSE : 0));
     const uint32_t nmo = nout * (S - 1);
     ls->leader_commit = c > committed0;
     ls->follower_commit = 0;
@@ -253,44 +399,43 @@ struct SteadyLeader : SteadyBase<RM> {
   }
 };
 
-template <int S, int RM>
-struct SteadyFollower : SteadyBase<RM> {
-  using B = SteadyBase<RM>;
+template <int S, int RM, class A = LaneAddr<S, RM>>
+struct SteadyFollower : SteadyBase<A> {
+  using B = SteadyBase<A>;
   using B::kp;
-  using B::i;
+  using B::a;
+  using Box = typename A::Box;
   GF_HD SteadyFollower(const StepParams& k, uint32_t lane, uint32_t peer) : B(k, lane, peer) {}
 
   GF_HD bool step(LaneStats* ls, uint32_t hint, uint32_t* hint_out) {
     const uint32_t hL = (hint >> WH_SLOT_SHIFT) & 7u;  // wave-uniform: the leader's slot
-    uint32_t gin[S], gout[S];
-    routes_of<S, RM>(kp, i, gin, gout);
     // ---- one load round
     const uint64_t hdr = ntld(B::s64(SR_HDR));
     const uint64_t term = ntld(B::s64(SR_TERM));
     const uint64_t hi0 = ntld(B::s64(SR_LAST_INDEX));
-    const uint32_t lw = kp.has_locals ? ntld(kp.ln.u32(LR_LWORD)[i]) : 0u;
+    const uint32_t lw = kp.has_locals ? ntld(a.lword()) : 0u;
+    // every in-mailbox's count byte, once: the leader slot's is cbL
     uint32_t other = 0;  // messages from any slot but hL
-    uint32_t gL = NOPOS, oL = NOPOS;
+    uint32_t cbL = 0;
 #pragma unroll
     for (int j = 0; j < S; ++j) {
-      const bool in = gin[j] != NOPOS;
-      const uint32_t b = in ? (uint32_t)ntld(B::min_at(gin[j]).cnt()) : 0u;
+      const uint32_t b = a.has_in(j) ? (uint32_t)ntld(a.min(j).cnt()) : 0u;
       other |= (uint32_t)j != hL ? mb_n(b) : 0u;
-      gL = (uint32_t)j == hL ? gin[j] : gL;
-      oL = (uint32_t)j == hL ? gout[j] : oL;
+      cbL = (uint32_t)j == hL ? b : cbL;
     }
-    const Mailbox mb = B::min_at(gL != NOPOS ? gL : 0u);
-    const uint32_t cbL = gL != NOPOS ? (uint32_t)ntld(mb.cnt()) : 0u;
-    const uint32_t fmt = gL != NOPOS ? ntld(mb.mterm()) : 0u;
+    bool inL;
+    const Box mb = a.in_of(hL, &inL);
+    const bool outL = a.has_out_of(hL);
+    const uint32_t fmt = inL ? ntld(mb.mterm()) : 0u;
     uint64_t li[2];
     uint32_t cd[2];
-    li[0] = gL != NOPOS ? ntld(mb.u64(0, MF_LOG_INDEX)) : 0ull;
-    cd[0] = gL != NOPOS ? ntld(mb.t32(0, MT_CDELTA)) : 0u;
+    li[0] = inL ? ntld(mb.u64(0, MF_LOG_INDEX)) : 0ull;
+    cd[0] = inL ? ntld(mb.t32(0, MT_CDELTA)) : 0u;
     // a shared mailbox (MB_SHARED, the steady state) repeats message 0's fields;
     // only an unshared pair loads the second, in a second round
     li[1] = li[0];
     cd[1] = cd[0];
-    if (gL != NOPOS && mb_n(cbL) >= 2 && !mb_shared(cbL)) {
+    if (inL && mb_n(cbL) >= 2 && !mb_shared(cbL)) {
       li[1] = ntld(mb.u64(1, MF_LOG_INDEX));
       cd[1] = ntld(mb.t32(1, MT_CDELTA));
     }
@@ -308,7 +453,7 @@ struct SteadyFollower : SteadyBase<RM> {
               h_nruns(hdr) >= 1 && h_gelo(hdr) && (flags & F_ETZ) && ((flags & F_LSLOT) >> F_LSLOT_SHIFT) == hL + 1 &&
               lw == 0 && other == 0 && !wide_term(term, 0, 0, 0);
     ok = ok && (c == 0 || ((cbL & MB_UNIFORM) && !(cbL & MB_RESP) && c <= 2 && (uint64_t)fmt == term));
-    ok = ok && (c == 0 || (oL != NOPOS && c <= kp.out.depth));
+    ok = ok && (c == 0 || (outL && c <= kp.out.depth));
     // ---- the Replicates, in arrival order
     uint64_t committed = committed0, hi = hi0, append_from = 0, out[2];
     uint32_t nent = 0;
@@ -338,8 +483,8 @@ struct SteadyFollower : SteadyBase<RM> {
     if (hi != hi0) ntst(B::s64(SR_LAST_INDEX), hi);
 #pragma unroll
     for (int j = 0; j < S; ++j) {
-      if (gout[j] == NOPOS) continue;
-      const Mailbox mo = B::mout_at(gout[j]);
+      if (!a.has_out(j)) continue;
+      const Box mo = a.mout(j);
       if ((uint32_t)j != hL || c == 0) {
         ntst(mo.cnt(), (uint8_t)0);
         continue;
@@ -352,8 +497,8 @@ struct SteadyFollower : SteadyBase<RM> {
       ntst(mo.mterm(), (uint32_t)term);
       ntst(mo.cnt(), (uint8_t)(c | MB_UNIFORM | MB_RESP | (shared ? MB_SHARED : 0u)));
     }
-    if (append_from) kp.ln.u64(LR_APPEND_FROM)[i] = append_from;
-    ntst(kp.ln.u8(LR_RFLAGS)[i], (uint8_t)(append_from ? RF_APPEND : 0));
+    if (append_from) a.append_from() = append_from;
+    ntst(a.rflags(), (uint8_t)(append_from ? RF_APPEND : 0));
     ls->leader_commit = 0;
     ls->follower_commit = committed > committed0;
     ls->escalated = 0;

@@ -137,6 +137,8 @@ def load_library(path=LIB_PATH):
         lib.gr_tick_all.argtypes = [c.c_void_p, c.c_uint32, c.c_uint64]
         lib.gr_splitmix64.argtypes = [c.c_uint64]
         lib.gr_splitmix64.restype = c.c_uint64
+    if hasattr(lib, "gr_steady_wave_uniform"):  # (older builds loaded for A/B runs lack it)
+        lib.gr_steady_wave_uniform.argtypes = [c.c_void_p]
     if path == LIB_PATH:
         _lib = lib
     _libs[path] = lib
@@ -508,6 +510,14 @@ class Engine:
         out_pos = np.ascontiguousarray(out_pos, np.uint32)
         n = in_pos.shape[1]
         _check(self.lib.gr_bind_routes(self._h, in_pos.ctypes.data, out_pos.ctypes.data, n), "gr_bind_routes")
+
+    def steady_wave_uniform(self):
+        """Whether the bound routes (and the last device pass's spaces) select the
+        steady kernel's wave-uniform addressing instance (gpuraft.h gr_steady_wave_uniform)."""
+        rc = self.lib.gr_steady_wave_uniform(self._h)
+        if rc < 0:
+            _check(rc, "gr_steady_wave_uniform")
+        return bool(rc)
 
     def set_locals(self, locals_):
         locals_ = np.ascontiguousarray(locals_, abi.LOCAL)

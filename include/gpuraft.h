@@ -556,6 +556,14 @@ int gr_space_cx_pack_host(void* space_host, uint32_t n_chunks, uint32_t position
 int gr_space_cx_unpack_host(void* space_host, uint32_t n_chunks, uint32_t positions, uint32_t depth,
                             const void* cx_host, const uint32_t* capacities, uint32_t side_capacity);
 int gr_bind_routes(gr_engine* e, const uint32_t* in_pos, const uint32_t* out_pos, uint32_t n_peers);
+/* 1 when the bound routes select the steady kernel's wave-uniform addressing
+ * instance for large gr_step_device passes, else 0: replica-major routes whose
+ * blocks (groups per replica block, and every mailbox block base) are multiples
+ * of 64, so that a wave's lanes are consecutive in every region they touch, and
+ * message spaces (those of the last gr_step_device pass) whose hot region ends at
+ * or below 4 GiB. GR_STEADY_WU=0 at gr_create keeps the per-lane instance (0
+ * here). Both instances compute the same pass. */
+int gr_steady_wave_uniform(gr_engine* e);
 int gr_set_locals(gr_engine* e, const gr_local_input* locals, size_t n);
 /* Launch one pass on `stream` (a hipStream_t, may be NULL) without syncing.
  * in_space/out_space are device pointers laid out by gr_space_bytes() with
