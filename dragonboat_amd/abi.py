@@ -102,6 +102,12 @@ QUIESCE_STATE = np.dtype([("tick", u64), ("election_tick", u64), ("quiesced_sinc
                           ("exit_quiesce_tick", u64), ("enabled", u8), ("pad", u8, (7,))])
 assert QUIESCE_STATE.itemsize == 48
 UPDATE_COMMIT = np.dtype([("stable_log_to", u64), ("stable_log_term", u64), ("applied_to", u64)])
+# gr_config_change (gr_apply_config_change): type numbered as raftpb.ConfigChangeType
+# (raftpb/raft.pb.go:167-169), status as gr_cc_status
+CC_ADD_NODE, CC_REMOVE_NODE, CC_ADD_OBSERVER = 0, 1, 2
+CC_APPLIED, CC_HOST, CC_NO_SLOT = 0, 1, 2
+CONFIG_CHANGE = np.dtype([("node_id", u64), ("rand", u64), ("type", u8), ("pad", u8, (7,))])
+assert CONFIG_CHANGE.itemsize == 24
 SIZES = {"gr_peer": 664, "gr_message": 80, "gr_local_input": 48, "gr_peer_result": 168,
          "gr_remote": 32, "gr_read_status": 32}
 assert PEER.itemsize == SIZES["gr_peer"], PEER.itemsize
@@ -177,7 +183,7 @@ MAX_ENTRY_SIZE = 2 * 32 * 1024 * 1024
 EXPORTS = [
     "gr_create", "gr_destroy", "gr_strerror", "gr_escalation_name", "gr_load_groups",
     "gr_sync_groups_to_host", "gr_step", "gr_inbox_reserve", "gr_release_outbox", "gr_stats_get", "gr_stats_reset",
-    "gr_load_peers", "gr_sync_peers_to_host", "gr_notify_applied", "gr_compact_log", "gr_commit_update", "gr_space_bytes", "gr_space_chunk_bytes",
+    "gr_load_peers", "gr_sync_peers_to_host", "gr_notify_applied", "gr_compact_log", "gr_commit_update", "gr_apply_config_change", "gr_space_bytes", "gr_space_chunk_bytes",
     "gr_space_hot_chunk_bytes", "gr_space_hot_tile_bytes", "gr_space_tile_positions", "gr_space_cold_used",
     "gr_space_side_bytes", "gr_space_side_pack", "gr_space_side_unpack", "gr_space_side_pack_host",
     "gr_space_side_unpack_host", "gr_space_cx_bytes", "gr_space_cx_pack", "gr_space_cx_unpack",

@@ -3,6 +3,7 @@
 - libgpuraft.so: the product, HIP for gfx950 (hipcc).
 - liboracle.so, kat_tests: the CPU oracle (g++), test infrastructure.
 - libhostlane.so: the engine's lane code compiled for the host, test-only.
+- libconfig_change_host.so: gr_config_change.h for the host and its reference side, test-only.
 Outputs stay in-tree (git-ignored) so they travel to the GPU box.
 """
 import os
@@ -18,7 +19,7 @@ CSRC = os.path.join(ROOT, "dragonboat_amd", "csrc")
 ENGINE_SRC = [os.path.join(CSRC, "gr_engine.hip")] + [os.path.join(CSRC, f"gr_kernels_s{s}.hip") for s in (1, 3, 5, 8)]
 ENGINE_DEPS = ENGINE_SRC + [os.path.join(CSRC, f)
                             for f in ("gr_lane.h", "gr_layout.h", "gr_host.h", "gr_fast.h", "gr_steady.h", "gr_tick.h", "gr_io.h",
-                                      "gr_cover.h", "gr_kernels.h", "gr_scan.h", "gr_quiesce.h")] + \
+                                      "gr_cover.h", "gr_kernels.h", "gr_scan.h", "gr_quiesce.h", "gr_config_change.h")] + \
     [os.path.join(ROOT, "include", "gpuraft.h")]
 JOBS = max(1, min(8, os.cpu_count() or 1))
 ENGINE_LIB = os.path.join(ROOT, "dragonboat_amd", "_build", "libgpuraft.so")
@@ -29,6 +30,7 @@ HOSTLANE_LIB = os.path.join(ROOT, "tests", "_build", "libhostlane.so")
 HOSTLANE_ELECT_LIB = os.path.join(ROOT, "tests", "_build", "libhostlane_elect.so")
 QUIESCE_HOST_LIB = os.path.join(ROOT, "tests", "_build", "libquiesce_host.so")
 STEADY_WU_HOST_LIB = os.path.join(ROOT, "tests", "_build", "libsteady_wu_host.so")
+CONFIG_CHANGE_HOST_LIB = os.path.join(ROOT, "tests", "_build", "libconfig_change_host.so")
 WIRE_SRC = os.path.join(ROOT, "dragonboat_amd", "csrc", "gr_wire.hip")
 WIRE_DEPS = [WIRE_SRC, os.path.join(ROOT, "include", "gpuraft_wire.h"), os.path.join(ROOT, "include", "gpuraft.h"),
              os.path.join(CSRC, "gr_scan.h")]
@@ -285,6 +287,30 @@ def build_steady_wu_host(force=False):
     return STEADY_WU_HOST_LIB
 
 
+def build_config_change_host(force=False):
+    """libconfig_change_host.so: gr_config_change.h (what gr_apply_config_change
+    runs on the device) compiled for the host over gr_peer records, and the
+    reference side (the oracle's raft object driven through its own
+    build_peer / export_peer), for tests/test_config_change.py."""
+    os.makedirs(os.path.dirname(CONFIG_CHANGE_HOST_LIB), exist_ok=True)
+    odir = os.path.join(ROOT, "oracle")
+    src = os.path.join(ROOT, "tests", "native", "config_change_host.hip")
+    ref = os.path.join(ROOT, "tests", "native", "config_change_ref.cpp")
+    deps = [src, ref, os.path.join(ROOT, "include", "gpuraft.h"), os.path.join(odir, "batch.cpp"),
+            os.path.join(odir, "raft_oracle.hpp")] + \
+        [os.path.join(CSRC, f) for f in ("gr_config_change.h", "gr_host.h", "gr_layout.h", "gr_quiesce.h")]
+    if not (force or _stale(CONFIG_CHANGE_HOST_LIB, deps)):
+        return CONFIG_CHANGE_HOST_LIB
+    with _locked(CONFIG_CHANGE_HOST_LIB):
+        if force or _stale(CONFIG_CHANGE_HOST_LIB, deps):
+            inc = ["-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-I" + odir]
+            objs = [CONFIG_CHANGE_HOST_LIB + ".host.o", CONFIG_CHANGE_HOST_LIB + ".ref.o"]
+            _run([HIPCC, "--cuda-host-only", "-O2", "-g", "-std=c++17", "-fPIC", *inc, "-c", src, "-o", objs[0]])
+            _run(["g++", "-std=c++17", "-O2", "-g", "-fPIC", *inc, "-c", ref, "-o", objs[1]])
+            _run([HIPCC, "-shared", "-fPIC", *objs, "-o", CONFIG_CHANGE_HOST_LIB, "-lpthread"])
+    return CONFIG_CHANGE_HOST_LIB
+
+
 ORACLE_SAN_LIB = os.path.join(ROOT, "oracle", "_build", "liboracle_san.so")
 KAT_SAN_BIN = os.path.join(ROOT, "oracle", "_build", "kat_tests_san")
 HOSTLANE_SAN_LIB = os.path.join(ROOT, "tests", "_build", "libhostlane_san.so")
@@ -373,5 +399,6 @@ def build_all(force=False):
         build_tools(force)
         build_quiesce_host(force)
         build_steady_wu_host(force)
+        build_config_change_host(force)
         for f in fs:
             f.result()

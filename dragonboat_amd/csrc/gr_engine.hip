@@ -658,6 +658,57 @@ int gr_commit_update(gr_engine* e, const uint32_t* slots, const gr_update_commit
   return *(uint32_t*)e->h_scal ? GR_ESTATE : GR_OK;
 }
 
+// Peer.ApplyConfigChange / RejectConfigChange (peer.go:153-174) for a slot list
+// (gr_config_change.h, gr_io.h config_rows): 24 bytes up and 4 down per record,
+// the membership itself never leaves the device.
+int gr_apply_config_change(gr_engine* e, const uint32_t* slots, const gr_config_change* cc, size_t n,
+                           int32_t* status) {
+  if (!e || (n && (!slots || !cc))) return GR_EINVAL;
+  if (n == 0) return GR_OK;
+  if (n >= 0x80000000ull) return GR_EINVAL;
+  const uint32_t cap = e->cfg.max_peers;
+  std::vector<uint64_t> seen((cap + 63) / 64, 0);
+  for (size_t x = 0; x < n; ++x) {
+    const uint32_t p = slots[x];
+    if (p >= cap || (seen[p >> 6] >> (p & 63)) & 1) return GR_ERANGE;  // nothing written
+    seen[p >> 6] |= 1ull << (p & 63);
+  }
+  std::lock_guard<std::mutex> guard(e->mu);
+  GR_REFUSE_PENDING(e);  // from here on as gr_compact_log, so the same states give the same codes
+  for (size_t x = 0; x < n; ++x)
+    if (!conf::known_type(cc[x].type)) return GR_EINVAL;  // "unexpected config change type", peer.go:166-167
+  HIPCHK(hipDeviceSynchronize());  // passes in flight on other streams own the rows
+  const hipStream_t s = e->stream;
+  int r;
+  if ((r = grow_device(&e->d_slots.p, &e->d_slots.n, n * 4))) return r;
+  if ((r = grow_device(&e->d_peers.p, &e->d_peers.n, n * (sizeof(gr_config_change) + 4) + 16))) return r;
+  if ((r = grow_device(&e->d_scal.p, &e->d_scal.n, 16))) return r;
+  if ((r = grow_pinned(&e->h_scal, &e->h_scal_bytes, 16))) return r;
+  gr_config_change* dcc = (gr_config_change*)e->d_peers.p;
+  int32_t* dst = (int32_t*)(dcc + n);
+  HIPCHK(hipMemcpyAsync(e->d_slots.p, slots, n * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(dcc, cc, n * sizeof(gr_config_change), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemsetAsync(e->d_scal.p, 0, 16, s));
+  const dim3 grid(io_grid(n)), blk(io::kIoBlock);
+  const uint32_t* ds = (const uint32_t*)e->d_slots.p;
+  uint32_t* refused = (uint32_t*)e->d_scal.p;
+  switch (e->S) {  // the instantiated slot counts (instantiated_slots)
+#define GR_CONFIG_CASE(SS)                                                                                         \
+  case SS:                                                                                                         \
+    hipLaunchKernelGGL(io::config_rows<SS>, grid, blk, 0, s, e->st, ds, (const gr_config_change*)dcc, (uint32_t)n, \
+                       dst, refused);                                                                              \
+    break;
+    GR_CONFIG_CASE(1) GR_CONFIG_CASE(3) GR_CONFIG_CASE(5) GR_CONFIG_CASE(8)
+#undef GR_CONFIG_CASE
+    default: return GR_EINVAL;
+  }
+  HIPCHK(hipGetLastError());
+  if (status) HIPCHK(hipMemcpyAsync(status, dst, n * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(e->h_scal, refused, 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return *(uint32_t*)e->h_scal ? GR_ESTATE : GR_OK;
+}
+
 // Peer.NotifyRaftLastApplied (peer.go:282-284) for a slot list: raft.applied =
 // the RSM's batched last applied index, as node.handleEvents does first in
 // every step (node.go:632-635,653). No other field changes.

@@ -26,6 +26,7 @@
 // packer uses (gr_host.h), so the records are bit-identical.
 #pragma once
 #include "gpuraft_wire.h"
+#include "gr_config_change.h"
 #include "gr_host.h"
 #include "gr_scan.h"
 
@@ -1406,6 +1407,19 @@ __global__ void commit_rows(StateBase st, const uint32_t* slots, const gr_update
                             int32_t* status, uint32_t* refused) {
   for (uint32_t x = io_tid(); x < n; x += io_stride()) {
     const int32_t rc = host::commit_marks(st, slots[x], uc[x]);
+    status[x] = rc;
+    if (rc) atomicOr(refused, 1u);
+  }
+}
+
+// gr_apply_config_change: Peer.ApplyConfigChange (peer.go:153-174) per listed
+// slot (gr_config_change.h). status: gr_cc_status; only GR_CC_APPLIED slots are
+// written. Slots and types were checked on the host.
+template <int S>
+__global__ void config_rows(StateBase st, const uint32_t* slots, const gr_config_change* cc, uint32_t n,
+                            int32_t* status, uint32_t* refused) {
+  for (uint32_t x = io_tid(); x < n; x += io_stride()) {
+    const int32_t rc = conf::apply_rows<S>(st, slots[x], cc[x]);
     status[x] = rc;
     if (rc) atomicOr(refused, 1u);
   }

@@ -61,6 +61,7 @@ def load_library(path=LIB_PATH):
     lib.gr_pair_messages.argtypes = [c.c_void_p, c.c_size_t, c.POINTER(c.c_size_t)]
     lib.gr_pack_locals.argtypes = [c.c_void_p, c.c_size_t, c.c_void_p, c.c_void_p, c.POINTER(c.c_size_t)]
     lib.gr_commit_update.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p]
+    lib.gr_apply_config_change.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p]
     lib.gr_step.argtypes = [c.c_void_p, c.POINTER(abi.Inbox), c.POINTER(abi.Outbox)]
     lib.gr_release_outbox.argtypes = [c.c_void_p, c.POINTER(abi.Outbox)]
     lib.gr_inbox_reserve.argtypes = [c.c_void_p, c.c_size_t, c.c_size_t, c.POINTER(abi.Inbox)]
@@ -305,6 +306,26 @@ class Engine:
                                        st.ctypes.data if len(st) else None)
         if rc not in (0, -6):
             _check(rc, "gr_commit_update")
+        return rc, st
+
+    def apply_config_change(self, slots, cc):
+        """Peer.ApplyConfigChange / RejectConfigChange on the device
+        (gr_apply_config_change): cc is an abi.CONFIG_CHANGE array, one record per
+        listed engine slot. Returns (rc, per-slot status: abi.CC_APPLIED, or
+        CC_HOST / CC_NO_SLOT for a peer left untouched, which the host syncs,
+        changes and reloads); rc is -6 (GR_ESTATE) when some status is not
+        CC_APPLIED. A slot out of range or listed twice, or an unknown type,
+        raises before anything is written, and so does a call refused while a
+        step_compact_begin is pending (GR_ESTATE with no status written)."""
+        slots = np.ascontiguousarray(slots, np.uint32)
+        cc = np.ascontiguousarray(cc, abi.CONFIG_CHANGE)
+        assert len(slots) == len(cc)
+        st = np.full(len(slots), -1, np.int32)  # no gr_cc_status: still there after a refused call
+        rc = self.lib.gr_apply_config_change(self._h, slots.ctypes.data if len(slots) else None,
+                                             cc.ctypes.data if len(cc) else None, len(slots),
+                                             st.ctypes.data if len(st) else None)
+        if rc not in (0, -6) or (rc == -6 and st[0] < 0):
+            _check(rc, "gr_apply_config_change")
         return rc, st
 
     def step(self, msgs=None, locals_=None):

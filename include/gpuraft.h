@@ -322,6 +322,61 @@ typedef struct gr_update_commit {
 } gr_update_commit;
 int gr_commit_update(gr_engine* e, const uint32_t* slots, const gr_update_commit* uc, size_t n, int32_t* status);
 
+/* Peer.ApplyConfigChange / Peer.RejectConfigChange (peer.go:153-174 ->
+ * raft.addNode / addObserver / removeNode, raft.go:822-861) for a list of engine
+ * slots: the RSM's apply path reports a committed membership change to every
+ * loaded replica of the group. Call it between passes. Per record 24 bytes and
+ * the 4-byte slot go up and a 4-byte status comes down; the group's state stays on the device.
+ *
+ * node_id 0 (NoLeader) only clears pendingConfigChange (peer.go:155-158, and
+ * RejectConfigChange). Otherwise, with pendingConfigChange cleared in every case:
+ *   GR_CC_REMOVE_NODE  the member slot holding node_id becomes GR_SLOT_EMPTY: its
+ *     match, next, snapshot_index, state and active read 0, remote_id stays. A
+ *     leader whose transfer target it was aborts the transfer. self_slot is
+ *     GR_SLOT_NONE on the peer that removed itself. If a voter is left,
+ *     tryCommit() runs in whatever state the peer is (raft.go:856-860).
+ *   GR_CC_ADD_NODE     a voter: nothing more. An observer: its slot becomes a
+ *     voter with its progress kept, and when it is the peer itself,
+ *     becomeFollower(term, leaderID) with `rand` as reset()'s draw
+ *     (raft.go:833-835). Else setRemote(id, 0, lastIndex + 1) into a free slot.
+ *   GR_CC_ADD_OBSERVER an observer: nothing more. Else setObserver(id, 0,
+ *     lastIndex + 1) into a free slot.
+ * A free slot is the empty slot whose remote_id is already node_id (a re-add),
+ * else the lowest empty slot that no live ReadIndex FIFO entry names in
+ * from_slot or ack_bits: readStatus.confirmed is keyed by node id
+ * (readindex.go:21-26) and a removed node's ack still counts, so a new node must
+ * not inherit its bit.
+ *
+ * status[x] (may be NULL): GR_CC_APPLIED, or the peer is left untouched, bit for
+ * bit, and the host takes the gr_sync_peers_to_host / Go / gr_load_peers route
+ * for it:
+ *   GR_CC_HOST    tryCommit() after a removal would raise committed (the
+ *     reference then broadcasts Replicates, which only a pass can send), or its
+ *     term lookup falls below the term-run window; the peer is a candidate (its
+ *     vote tally overlays the FIFO ack rows by slot); AddObserver of a voter (the
+ *     reference holds the id in both maps); a promoted observer without an
+ *     election timeout (the reference panics in reset()).
+ *   GR_CC_NO_SLOT no free slot.
+ * Returns GR_ESTATE when some status is not GR_CC_APPLIED. Slots out of range
+ * or listed twice: GR_ERANGE; a type that is no gr_cc_type: GR_EINVAL (the
+ * reference panics, peer.go:166-167); both before anything is written. Refused
+ * while a gr_step_compact_begin is pending, as gr_compact_log: that is GR_ESTATE
+ * too, with nothing applied and `status` not written. No gr_cc_status is
+ * negative, so a caller that fills `status` with -1 before the call tells the
+ * two apart: after GR_ESTATE, status[0] still -1 means the call was refused and
+ * did nothing; otherwise every status[x] was written. The quiesce records are
+ * not touched: no call site of ApplyConfigChange tells the manager. */
+enum gr_cc_type { GR_CC_ADD_NODE = 0, GR_CC_REMOVE_NODE = 1, GR_CC_ADD_OBSERVER = 2 }; /* raftpb/raft.pb.go:167-169 */
+enum gr_cc_status { GR_CC_APPLIED = 0, GR_CC_HOST = 1, GR_CC_NO_SLOT = 2 };
+typedef struct gr_config_change {
+  uint64_t node_id;
+  uint64_t rand; /* the next random.LockGuardedRand.Uint64() draw, as gr_local_input.rand */
+  uint8_t type;  /* gr_cc_type */
+  uint8_t pad[7];
+} gr_config_change;
+int gr_apply_config_change(gr_engine* e, const uint32_t* slots, const gr_config_change* cc, size_t n,
+                           int32_t* status);
+
 /* One synchronous pass over host buffers (what a cgo caller uses). */
 int gr_step(gr_engine* e, const gr_inbox* in, gr_outbox* out);
 /* Engine-owned pinned buffers for the next gr_step's inbox: sets in->msgs /
@@ -435,7 +490,7 @@ int gr_step_compact(gr_engine* e, const gr_cinbox* in, gr_coutbox* out);
  * pending pass owns the engine's scratch and lane rows: every other call on
  * that engine that steps it or uses them (gr_step, gr_step_compact{,_begin},
  * gr_step_device, gr_load_* / gr_sync_*, gr_set_locals, gr_bind_routes,
- * gr_compact_log, gr_commit_update, gr_notify_applied, gr_collect_results,
+ * gr_compact_log, gr_commit_update, gr_apply_config_change, gr_notify_applied, gr_collect_results,
  * gr_space_cold_used) returns GR_ESTATE and changes nothing. */
 int gr_step_compact_begin(gr_engine* e, const gr_cinbox* in);
 int gr_step_compact_end(gr_engine* e, gr_coutbox* out);
