@@ -108,6 +108,13 @@ CC_ADD_NODE, CC_REMOVE_NODE, CC_ADD_OBSERVER = 0, 1, 2
 CC_APPLIED, CC_HOST, CC_NO_SLOT = 0, 1, 2
 CONFIG_CHANGE = np.dtype([("node_id", u64), ("rand", u64), ("type", u8), ("pad", u8, (7,))])
 assert CONFIG_CHANGE.itemsize == 24
+# gr_snapshot_rec / gr_restored / gr_membership (gpuraft.h, snapshots on the device)
+SNAPSHOT_REC = np.dtype([("index", u64), ("term", u64)])
+assert SNAPSHOT_REC.itemsize == 16
+RESTORED = np.dtype([("peer", u32), ("pad", u32), ("index", u64), ("term", u64)])
+assert RESTORED.itemsize == 24
+MEMBERSHIP = np.dtype([("node_id", u64, (GR_SMAX,)), ("kind", u8, (GR_SMAX,)), ("rand", u64)])
+assert MEMBERSHIP.itemsize == 80
 SIZES = {"gr_peer": 664, "gr_message": 80, "gr_local_input": 48, "gr_peer_result": 168,
          "gr_remote": 32, "gr_read_status": 32}
 assert PEER.itemsize == SIZES["gr_peer"], PEER.itemsize
@@ -194,6 +201,8 @@ EXPORTS = [
     "gr_bind_nodes", "gr_step_wire", "gr_step_wire_compact",
     "gr_graph_capture", "gr_graph_replay", "gr_graph_destroy",
     "gr_set_elections", "gr_get_elections", "gr_promotions",
+    "gr_set_snapshots", "gr_get_snapshots", "gr_set_snapshot_recs", "gr_get_snapshot_recs", "gr_restored_snapshots",
+    "gr_restore_remotes",
     "gr_set_quiesce", "gr_get_quiesce", "gr_load_quiesce", "gr_sync_quiesce", "gr_load_quiesce_peers",
     "gr_sync_quiesce_peers", "gr_tick_all", "gr_splitmix64",
 ]

@@ -214,5 +214,88 @@ GR_HD int32_t apply_rows(const StateBase& st, uint32_t p, const gr_config_change
   return rc;
 }
 
+// ---------------------------------------------------------------- restoreRemotes
+// Peer.RestoreRemotes (peer.go:177-180 -> raft.restoreRemotes, raft.go:327-355)
+// behind gr_restore_remotes, by the same read-record / transform / write-record
+// scheme. The reference rebuilds both maps from the snapshot's membership:
+// every listed id gets remote{match: 0 or lastIndex for the peer itself, next:
+// lastIndex + 1}, every other member is gone. Before it sets a voter that it
+// holds as an observer it runs becomeFollower(term, leaderID) (:329-333), whose
+// reset() draws once: two such ids need two draws and go to the host.
+
+// The list's length (the first GR_SLOT_EMPTY kind ends it).
+GR_HD uint32_t listed(const gr_membership& m) {
+  uint32_t n = 0;
+  while (n < (uint32_t)GR_SMAX && m.kind[n] != GR_SLOT_EMPTY) n++;
+  return n;
+}
+GR_HD bool known_kinds(const gr_membership& m) {
+  for (uint32_t k = 0; k < listed(m); ++k)
+    if (m.kind[k] != GR_SLOT_VOTER && m.kind[k] != GR_SLOT_OBSERVER) return false;
+  return true;
+}
+
+// One membership on one record. Anything but GR_CC_APPLIED: g holds garbage and
+// the caller keeps the peer as it was.
+GR_HD int32_t restore_remotes(gr_peer& g, uint32_t S, const gr_membership& m) {
+  if (g.state == GR_CANDIDATE) return GR_CC_HOST;  // as apply(): the tally overlays the ack rows by slot
+  const uint32_t n = listed(m);
+  uint32_t promoted = 0;
+  for (uint32_t k = 0; k < n; ++k) {
+    for (uint32_t x = 0; x < k; ++x)
+      if (m.node_id[x] == m.node_id[k]) return GR_CC_HOST;  // an id in both maps, or twice in one
+    const uint32_t j = member_slot(g, S, m.node_id[k]);
+    if (m.kind[k] == GR_SLOT_VOTER && j != GR_SLOT_NONE && g.remotes[j].kind == GR_SLOT_OBSERVER) promoted++;
+  }
+  if (promoted > 1) return GR_CC_HOST;
+  if (promoted) {
+    const int32_t rc = become_follower(g, S, m.rand);  // keeps leaderID; clears the FIFO
+    if (rc != GR_CC_APPLIED) return rc;
+  }
+  // members that are not listed go; their slots keep their ids
+  for (uint32_t j = 0; j < S; ++j) {
+    if (g.remotes[j].kind == GR_SLOT_EMPTY) continue;
+    bool keep = false;
+    for (uint32_t k = 0; k < n; ++k) keep = keep || m.node_id[k] == g.remote_id[j];
+    if (!keep) drop_member(g, j);
+  }
+  // an id keeps the slot that carries it, live or empty: the mailbox routes
+  // bound to that slot stay valid
+  for (uint32_t k = 0; k < n; ++k) {
+    uint32_t j = member_slot(g, S, m.node_id[k]);
+    for (uint32_t x = 0; x < S; ++x)
+      if (j == GR_SLOT_NONE && g.remotes[x].kind == GR_SLOT_EMPTY && g.remote_id[x] == m.node_id[k]) j = x;
+    if (j == GR_SLOT_NONE) continue;
+    set_member(g, j, m.node_id[k], m.kind[k]);
+    if (m.node_id[k] == g.node_id) g.remotes[j].match = g.last_index;
+  }
+  // the others take free slots by apply()'s rule
+  for (uint32_t k = 0; k < n; ++k) {
+    if (member_slot(g, S, m.node_id[k]) != GR_SLOT_NONE) continue;
+    const uint32_t f = free_slot(g, S, m.node_id[k]);
+    if (f == GR_SLOT_NONE) return GR_CC_NO_SLOT;
+    set_member(g, f, m.node_id[k], m.kind[k]);
+    if (m.node_id[k] == g.node_id) g.remotes[f].match = g.last_index;
+  }
+  set_self_slot(g, S);
+  return GR_CC_APPLIED;
+}
+
+template <int S>
+GR_HD int32_t restore_rows(const StateBase& st, uint32_t p, const gr_membership& m) {
+  constexpr uint32_t n64 = SR_REMOTE + 4 * S + 3 * GR_Q, n8 = 2 * GR_Q;  // rows_u64(S), rows_u8(S)
+  gr_peer g;
+  memset(&g, 0, sizeof(g));
+  const uint64_t old = st.u64(SR_HDR)[p];
+  for (uint32_t r = 0; r < n64; ++r) host::set_u64_row(g, r, S, st.u64(r)[p]);
+  host::resolve_sync(g, S, old);
+  for (uint32_t r = 0; r < n8; ++r) host::set_u8_row(g, r, S, st.u8(r)[p]);
+  const int32_t rc = restore_remotes(g, S, m);
+  if (rc != GR_CC_APPLIED) return rc;
+  for (uint32_t r = 0; r < n64; ++r) st.u64(r)[p] = r == SR_HDR ? header_after(g, S, old) : host::get_u64_row(g, r, S);
+  for (uint32_t r = 0; r < n8; ++r) st.u8(r)[p] = host::get_u8_row(g, r, S);
+  return rc;
+}
+
 }  // namespace conf
 }  // namespace gr

@@ -76,6 +76,16 @@ enum CoverElectId : uint32_t { GR_COVER_ELECT_IDS(GR_COVER_ENUM) CE_N };
 enum CoverQuiesceId : uint32_t { GR_COVER_QUIESCE_IDS(GR_COVER_ENUM) CQ_N };
 #undef GR_COVER_ENUM
 
+// The snapshot handlers' ids (gr_lane.h with StepParams::snapshots): a fourth
+// table, read out through gr_coverage_snap_read, so the first three stay as they
+// are.
+#define GR_COVER_SNAP_IDS(X)                                                                  \
+  X(SEND_INACTIVE) X(SEND_INSTALL) X(SEND_EMPTY_SNAPSHOT) X(F_INSTALL) X(O_INSTALL) X(C_INSTALL) \
+  X(IGNORED_COMMITTED) X(MATCH_COMMIT) X(RESTORE) X(REJECT_PANIC)
+#define GR_COVER_ENUM(n) CS_##n,
+enum CoverSnapId : uint32_t { GR_COVER_SNAP_IDS(GR_COVER_ENUM) CS_N };
+#undef GR_COVER_ENUM
+
 #ifdef GR_COVERAGE
 // one array per code object (the kernels of each slot count are their own translation unit)
 static __device__ unsigned long long gr_cover_dev[CV_N];
@@ -100,6 +110,16 @@ __host__ __device__ static inline void cover_quiesce_hit(uint32_t id) {
 #endif
 }
 #define GR_COVER_Q(id) ::gr::cover_quiesce_hit(::gr::CQ_##id)
+static __device__ unsigned long long gr_cover_snap_dev[CS_N];
+inline unsigned long long gr_cover_snap_host[CS_N];
+__host__ __device__ static inline void cover_snap_hit(uint32_t id) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  atomicAdd(&gr_cover_snap_dev[id], 1ull);
+#else
+  gr_cover_snap_host[id]++;
+#endif
+}
+#define GR_COVER_S(id) ::gr::cover_snap_hit(::gr::CS_##id)
 __host__ __device__ static inline void cover_hit(uint32_t id) {
 #if defined(__HIP_DEVICE_COMPILE__)
   atomicAdd(&gr_cover_dev[id], 1ull);
@@ -114,6 +134,7 @@ __host__ __device__ static inline void cover_hit(uint32_t id) {
 #define GR_COVER(id) ((void)0)
 #define GR_COVER_E(id) ((void)0)
 #define GR_COVER_Q(id) ((void)0)
+#define GR_COVER_S(id) ((void)0)
 #define GR_COVER_ESC(e) ((void)0)
 #define GR_CHECK_INV(cond, id) ((void)0)
 #endif

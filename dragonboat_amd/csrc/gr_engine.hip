@@ -42,6 +42,10 @@ extern template hipError_t cover_quiesce_read<1>(uint64_t*);
 extern template hipError_t cover_quiesce_read<3>(uint64_t*);
 extern template hipError_t cover_quiesce_read<5>(uint64_t*);
 extern template hipError_t cover_quiesce_read<8>(uint64_t*);
+extern template hipError_t cover_snap_read<1>(uint64_t*);
+extern template hipError_t cover_snap_read<3>(uint64_t*);
+extern template hipError_t cover_snap_read<5>(uint64_t*);
+extern template hipError_t cover_snap_read<8>(uint64_t*);
 #endif
 
 // tick_lanes: launch the tick kernel (some lane may carry ticks or a ReadIndex).
@@ -117,6 +121,12 @@ struct gr_engine {
   // the promotion list (gr_promotions): a 16-byte header (count, overflow flag)
   // and max_peers gr_promotion records, one device allocation
   uint8_t* promo = nullptr;
+  uint8_t snapshots = 0;          // StepParams::snapshots (gr_set_snapshots; GR_SNAPSHOTS=1 at gr_create)
+  // the groups' snapshot records (gr_set_snapshot_recs): max_peers records,
+  // zeroed; and the restored list (gr_restored_snapshots), laid out as promo
+  // with kRestStage records per engine slot
+  gr_snapshot_rec* snap_rec = nullptr;  // max_peers records, then the lanes' staging records (kRestStage each)
+  uint8_t* rest = nullptr;
   // the quiesce manager (gr_set_quiesce; GR_QUIESCE_ON_DEVICE=1 at gr_create):
   // one allocation, made by the first gr_load_quiesce or when the switch first
   // goes on, of cap records (qrec), as many pre-pass records (qprev), the words
@@ -252,6 +262,12 @@ StepParams base_params(gr_engine* e) {
   kp.promo_hdr = (uint32_t*)e->promo;
   kp.promo = (gr_promotion*)(e->promo + kPromoHeader);
   kp.promo_cap = e->cfg.max_peers;
+  kp.snapshots = e->snapshots;
+  kp.snap_rec = e->snap_rec;
+  kp.rest_stage = e->snap_rec + e->cfg.max_peers;
+  kp.rest_hdr = (uint32_t*)e->rest;
+  kp.rest = (gr_restored*)(e->rest + kPromoHeader);
+  kp.rest_cap = kRestStage * e->cfg.max_peers;
   kp.quiesce = e->quiesce;
   kp.qrec = e->qrec;
   kp.qprev = e->qprev;
@@ -460,6 +476,7 @@ int gr_create(const gr_config* cfg, gr_engine** out) {
   }
   if (const char* wu = getenv("GR_STEADY_WU")) e->wu_enabled = !(wu[0] == '0' && wu[1] == 0);
   if (const char* el = getenv("GR_ELECTIONS")) e->elections = el[0] == '1';
+  if (const char* sn = getenv("GR_SNAPSHOTS")) e->snapshots = sn[0] == '1';
   const char* qd = getenv("GR_QUIESCE_ON_DEVICE");
   if (const char* wc = getenv("GR_WAVE_CLOCK")) {
     // two regions: the general kernel's waves, then the tick kernel's (gr_kernels.h)
@@ -475,6 +492,8 @@ int gr_create(const gr_config* cfg, gr_engine** out) {
       hipMalloc((void**)&e->counters, 2 * kCounters * kCounterStride * 4) != hipSuccess ||
       hipMalloc((void**)&e->route_base, 2 * GR_SMAX * GR_SMAX * 4) != hipSuccess ||
       hipMalloc((void**)&e->promo, kPromoHeader + (size_t)cfg->max_peers * sizeof(gr_promotion)) != hipSuccess ||
+      hipMalloc((void**)&e->snap_rec, (size_t)cfg->max_peers * (1 + kRestStage) * sizeof(gr_snapshot_rec)) != hipSuccess ||
+      hipMalloc((void**)&e->rest, kPromoHeader + (size_t)kRestStage * cfg->max_peers * sizeof(gr_restored)) != hipSuccess ||
       hipMalloc((void**)&e->hints, 2 * hint_stride(e->cap)) != hipSuccess) {
     if (ds) (void)hipFree(ds);
     if (dl) (void)hipFree(dl);
@@ -490,6 +509,8 @@ int gr_create(const gr_config* cfg, gr_engine** out) {
       hipMemset(e->counters, 0, 2 * kCounters * kCounterStride * 4) != hipSuccess ||
       hipMemset(e->hints, 0, 2 * hint_stride(e->cap)) != hipSuccess ||
       hipMemset(e->promo, 0, kPromoHeader) != hipSuccess ||
+      hipMemset(e->snap_rec, 0, (size_t)cfg->max_peers * (1 + kRestStage) * sizeof(gr_snapshot_rec)) != hipSuccess ||
+      hipMemset(e->rest, 0, kPromoHeader) != hipSuccess ||
       hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess) {
     gr_destroy(e);
     return GR_EDEVICE;
@@ -523,6 +544,8 @@ void gr_destroy(gr_engine* e) {
   if (e->route_base) (void)hipFree(e->route_base);
   if (e->hints) (void)hipFree(e->hints);
   if (e->promo) (void)hipFree(e->promo);
+  if (e->snap_rec) (void)hipFree(e->snap_rec);
+  if (e->rest) (void)hipFree(e->rest);
   if (e->qmem) (void)hipFree(e->qmem);
   if (e->tail_hint) (void)hipHostFree(e->tail_hint);
   if (e->wclock) {
@@ -707,6 +730,100 @@ int gr_apply_config_change(gr_engine* e, const uint32_t* slots, const gr_config_
   HIPCHK(hipMemcpyAsync(e->h_scal, refused, 4, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   return *(uint32_t*)e->h_scal ? GR_ESTATE : GR_OK;
+}
+
+// Peer.RestoreRemotes (peer.go:177-180) for a slot list (gr_config_change.h
+// restore_rows, gr_io.h restore_remote_rows): the 80-byte membership and the
+// slot go up, a status comes down. Checks and refusals in gr_apply_config_change's order.
+int gr_restore_remotes(gr_engine* e, const uint32_t* slots, const gr_membership* ms, size_t n, int32_t* status) {
+  if (!e || (n && (!slots || !ms))) return GR_EINVAL;
+  if (n == 0) return GR_OK;
+  if (n >= 0x80000000ull) return GR_EINVAL;
+  const uint32_t cap = e->cfg.max_peers;
+  std::vector<uint64_t> seen((cap + 63) / 64, 0);
+  for (size_t x = 0; x < n; ++x) {
+    const uint32_t p = slots[x];
+    if (p >= cap || (seen[p >> 6] >> (p & 63)) & 1) return GR_ERANGE;  // nothing written
+    seen[p >> 6] |= 1ull << (p & 63);
+  }
+  std::lock_guard<std::mutex> guard(e->mu);
+  GR_REFUSE_PENDING(e);
+  for (size_t x = 0; x < n; ++x)
+    if (!conf::known_kinds(ms[x])) return GR_EINVAL;
+  HIPCHK(hipDeviceSynchronize());  // passes in flight on other streams own the rows
+  const hipStream_t s = e->stream;
+  int r;
+  if ((r = grow_device(&e->d_slots.p, &e->d_slots.n, n * 4))) return r;
+  if ((r = grow_device(&e->d_peers.p, &e->d_peers.n, n * (sizeof(gr_membership) + 4) + 16))) return r;
+  if ((r = grow_device(&e->d_scal.p, &e->d_scal.n, 16))) return r;
+  if ((r = grow_pinned(&e->h_scal, &e->h_scal_bytes, 16))) return r;
+  gr_membership* dms = (gr_membership*)e->d_peers.p;
+  int32_t* dst = (int32_t*)(dms + n);
+  HIPCHK(hipMemcpyAsync(e->d_slots.p, slots, n * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(dms, ms, n * sizeof(gr_membership), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemsetAsync(e->d_scal.p, 0, 16, s));
+  const dim3 grid(io_grid(n)), blk(io::kIoBlock);
+  const uint32_t* ds = (const uint32_t*)e->d_slots.p;
+  uint32_t* refused = (uint32_t*)e->d_scal.p;
+  switch (e->S) {  // the instantiated slot counts (instantiated_slots)
+#define GR_RESTORE_CASE(SS)                                                                                     \
+  case SS:                                                                                                      \
+    hipLaunchKernelGGL(io::restore_remote_rows<SS>, grid, blk, 0, s, e->st, ds, (const gr_membership*)dms,      \
+                       (uint32_t)n, dst, refused);                                                              \
+    break;
+    GR_RESTORE_CASE(1) GR_RESTORE_CASE(3) GR_RESTORE_CASE(5) GR_RESTORE_CASE(8)
+#undef GR_RESTORE_CASE
+    default: return GR_EINVAL;
+  }
+  HIPCHK(hipGetLastError());
+  if (status) HIPCHK(hipMemcpyAsync(status, dst, n * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(e->h_scal, refused, 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return *(uint32_t*)e->h_scal ? GR_ESTATE : GR_OK;
+}
+
+// The snapshot records of a slot list (gpuraft.h): a side array, no state row.
+static int transfer_snapshot_recs(gr_engine* e, const uint32_t* slots, gr_snapshot_rec* host, size_t n, bool to_device) {
+  if (!e || (n && (!slots || !host))) return GR_EINVAL;
+  if (n == 0) return GR_OK;
+  if (n >= 0x80000000ull) return GR_EINVAL;
+  const uint32_t cap = e->cfg.max_peers;
+  std::vector<uint64_t> seen((cap + 63) / 64, 0);
+  for (size_t x = 0; x < n; ++x) {
+    const uint32_t p = slots[x];
+    if (p >= cap || (seen[p >> 6] >> (p & 63)) & 1) return GR_ERANGE;  // nothing written
+    seen[p >> 6] |= 1ull << (p & 63);
+  }
+  std::lock_guard<std::mutex> guard(e->mu);
+  GR_REFUSE_PENDING(e);
+  HIPCHK(hipDeviceSynchronize());  // passes in flight on other streams read and write the records
+  const hipStream_t s = e->stream;
+  const size_t bytes = n * sizeof(gr_snapshot_rec);
+  int r;
+  if ((r = grow_device(&e->d_slots.p, &e->d_slots.n, n * 4))) return r;
+  if ((r = grow_device(&e->d_peers.p, &e->d_peers.n, bytes))) return r;
+  gr_snapshot_rec* d = (gr_snapshot_rec*)e->d_peers.p;
+  HIPCHK(hipMemcpyAsync(e->d_slots.p, slots, n * 4, hipMemcpyHostToDevice, s));
+  const dim3 grid(io_grid(n)), blk(io::kIoBlock);
+  if (to_device) {
+    HIPCHK(hipMemcpyAsync(d, host, bytes, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(io::set_snapshot_recs, grid, blk, 0, s, e->snap_rec, (const uint32_t*)e->d_slots.p,
+                       (const gr_snapshot_rec*)d, (uint32_t)n);
+    HIPCHK(hipGetLastError());
+  } else {
+    hipLaunchKernelGGL(io::get_snapshot_recs, grid, blk, 0, s, (const gr_snapshot_rec*)e->snap_rec,
+                       (const uint32_t*)e->d_slots.p, d, (uint32_t)n);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(host, d, bytes, hipMemcpyDeviceToHost, s));
+  }
+  HIPCHK(hipStreamSynchronize(s));
+  return GR_OK;
+}
+int gr_set_snapshot_recs(gr_engine* e, const uint32_t* slots, const gr_snapshot_rec* recs, size_t n) {
+  return transfer_snapshot_recs(e, slots, const_cast<gr_snapshot_rec*>(recs), n, true);
+}
+int gr_get_snapshot_recs(gr_engine* e, const uint32_t* slots, gr_snapshot_rec* out, size_t n) {
+  return transfer_snapshot_recs(e, slots, out, n, false);
 }
 
 // Peer.NotifyRaftLastApplied (peer.go:282-284) for a slot list: raft.applied =
@@ -1942,6 +2059,16 @@ int gr_set_elections(gr_engine* e, int on) {
 
 int gr_get_elections(const gr_engine* e) { return e ? (int)e->elections : GR_EINVAL; }
 
+int gr_set_snapshots(gr_engine* e, int on) {
+  if (!e) return GR_EINVAL;
+  std::lock_guard<std::mutex> guard(e->mu);
+  GR_REFUSE_PENDING(e);
+  e->snapshots = on ? 1 : 0;
+  return GR_OK;
+}
+
+int gr_get_snapshots(const gr_engine* e) { return e ? (int)e->snapshots : GR_EINVAL; }
+
 int gr_set_quiesce(gr_engine* e, int on) {
   if (!e) return GR_EINVAL;
   std::lock_guard<std::mutex> guard(e->mu);
@@ -2069,6 +2196,26 @@ int gr_promotions(gr_engine* e, gr_promotion* out, size_t cap, size_t* n) {
   return hdr[1] ? GR_ECAPACITY : GR_OK;
 }
 
+// The restored list, drained as gr_promotions drains its own.
+int gr_restored_snapshots(gr_engine* e, gr_restored* out, size_t cap, size_t* n) {
+  if (!e || !n || (cap && !out)) return GR_EINVAL;
+  *n = 0;
+  std::lock_guard<std::mutex> guard(e->mu);
+  GR_REFUSE_PENDING(e);
+  HIPCHK(hipDeviceSynchronize());  // passes may run on the caller's streams (gr_step_device, graph replays)
+  uint32_t hdr[2] = {0, 0};
+  HIPCHK(hipMemcpy(hdr, e->rest, sizeof(hdr), hipMemcpyDeviceToHost));
+  const size_t have = std::min<size_t>(hdr[0], (size_t)kRestStage * e->cfg.max_peers);
+  if (have > cap) {  // nothing drained: the caller comes back with room
+    *n = have;
+    return GR_ECAPACITY;
+  }
+  if (have) HIPCHK(hipMemcpy(out, e->rest + kPromoHeader, have * sizeof(gr_restored), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemset(e->rest, 0, 4));  // the count; the overflow flag stays
+  *n = have;
+  return hdr[1] ? GR_ECAPACITY : GR_OK;
+}
+
 #ifdef GR_COVERAGE
 // Coverage build only (libgpuraft_cover.so): per-branch hit counts (gr_cover.h).
 int gr_coverage_read(uint64_t* out, uint32_t n) {
@@ -2116,6 +2263,22 @@ int gr_coverage_quiesce_read(uint64_t* out, uint32_t n) {
 const char* gr_coverage_quiesce_names() {
 #define GR_COVER_NAME(x) #x ","
   return GR_COVER_QUIESCE_IDS(GR_COVER_NAME);
+#undef GR_COVER_NAME
+}
+// The snapshot handlers' table (gr_cover.h GR_COVER_SNAP_IDS), read the same way.
+int gr_coverage_snap_read(uint64_t* out, uint32_t n) {
+  if (!out || n < CS_N) return GR_EINVAL;
+  HIPCHK(hipDeviceSynchronize());
+  for (uint32_t k = 0; k < CS_N; ++k) out[k] = 0;
+  HIPCHK(cover_snap_read<1>(out));
+  HIPCHK(cover_snap_read<3>(out));
+  HIPCHK(cover_snap_read<5>(out));
+  HIPCHK(cover_snap_read<8>(out));
+  return (int)CS_N;
+}
+const char* gr_coverage_snap_names() {
+#define GR_COVER_NAME(x) #x ","
+  return GR_COVER_SNAP_IDS(GR_COVER_NAME);
 #undef GR_COVER_NAME
 }
 #endif

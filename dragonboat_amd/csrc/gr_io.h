@@ -1425,5 +1425,27 @@ __global__ void config_rows(StateBase st, const uint32_t* slots, const gr_config
   }
 }
 
+// gr_restore_remotes: Peer.RestoreRemotes (peer.go:177-180) per listed slot
+// (gr_config_change.h restore_rows). status: gr_cc_status; only GR_CC_APPLIED
+// slots are written. Slots and kinds were checked on the host.
+template <int S>
+__global__ void restore_remote_rows(StateBase st, const uint32_t* slots, const gr_membership* ms, uint32_t n,
+                                    int32_t* status, uint32_t* refused) {
+  for (uint32_t x = io_tid(); x < n; x += io_stride()) {
+    const int32_t rc = conf::restore_rows<S>(st, slots[x], ms[x]);
+    status[x] = rc;
+    if (rc) atomicOr(refused, 1u);
+  }
+}
+
+// gr_set_snapshot_recs / gr_get_snapshot_recs: the side array of snapshot
+// records over a slot list (slots checked on the host: in range, each once).
+__global__ void set_snapshot_recs(gr_snapshot_rec* recs, const uint32_t* slots, const gr_snapshot_rec* in, uint32_t n) {
+  for (uint32_t x = io_tid(); x < n; x += io_stride()) recs[slots[x]] = in[x];
+}
+__global__ void get_snapshot_recs(const gr_snapshot_rec* recs, const uint32_t* slots, gr_snapshot_rec* out, uint32_t n) {
+  for (uint32_t x = io_tid(); x < n; x += io_stride()) out[x] = recs[slots[x]];
+}
+
 }  // namespace io
 }  // namespace gr

@@ -11,7 +11,8 @@
 // state up to the escalating item, so every item is applied either entirely on
 // the device or entirely by the host (one source of truth).
 // Elections (campaign, votes, promotion: the "elections" section below) run
-// here only with StepParams::elections set; off, they escalate.
+// here only with StepParams::elections set; off, they escalate. So do snapshots
+// (send and restore: the "snapshots" section) with StepParams::snapshots.
 //
 // Function-level citations are to /root/reference/internal/raft/*.go.
 #pragma once
@@ -52,6 +53,7 @@ enum : uint32_t {
   D_RETIMEOUT = 1u << 8, D_STATE = 1u << 9, D_FLAGS = 1u << 10, D_WIN = 1u << 11,
   D_REM = 1u << 12, D_SNAP = 1u << 13, D_RI = 1u << 14, D_INMEM = 1u << 15,
   D_TALLY = 1u << 16,
+  D_RESTORE = 1u << 17,  // a restore: firstIndex-1 and entryLog.applied (with D_HI, D_COMMITTED, D_WIN, D_INMEM)
 };
 
 GR_HD bool is_leader_message(uint32_t t) {  // raft.go:986-989
@@ -136,7 +138,11 @@ struct Lane {
   // from TimeoutNow (raft.isLeaderTransferTarget, set for that campaign only)
   bool promoted = false, transfer_target = false;
   uint64_t promo_term = 0, promo_index = 0;
-
+  // snapshots: how many restores this pass has made. Their (index, term) pairs
+  // wait in the peer's staging records (StepParams::rest_stage), not in
+  // registers; after the run that stands they become gr_restored records, as the
+  // promotion does, and the last one the group's snapshot record.
+  uint32_t nrest = 0;
 
   // The general kernel's message prefetch (round 5, device builds, S <= 3): the
   // first kPfK messages of every in-mailbox, loaded before the message loop by
@@ -278,6 +284,10 @@ struct Lane {
     if (dirty & D_INMEM) {
       s64(SR_MARKER) = imk;
       s64(SR_SAVED_TO) = isv;
+    }
+    if (dirty & D_RESTORE) {  // entryLog.restore (logentry.go:376-381): firstIndex-1 and applied
+      s64(SR_LO) = lo;
+      s64(SR_LOG_APPLIED) = lo;
     }
     if (dirty & D_WIN) {
 #pragma unroll
@@ -816,8 +826,11 @@ struct Lane {
     m.log_index = nx - 1;
     m.log_term = lt;
     m.commit = committed;
-    if (nx <= hi) {  // entries(next, maxSize), logentry.go:231-236
-      if (nx <= lo) return GR_ESC_SNAPSHOT;  // checkBound -> ErrCompacted
+    if (nx <= hi && nx <= lo) {  // entries(): checkBound -> ErrCompacted, the InstallSnapshot branch
+      if (!snapshots()) return GR_ESC_SNAPSHOT;
+      const int e = snapshot_message(j, m);  // 0: m is the InstallSnapshot; below 0: nothing to send
+      if (e) return e < 0 ? 0 : e;
+    } else if (nx <= hi) {  // entries(next, maxSize), logentry.go:231-236
       if (nruns == 0 || nx < rs[0]) return GR_ESC_TERM_WINDOW;
       const uint64_t cnt = hi - nx + 1;
       if (cnt > 0xFFFFFFFFull) return GR_ESC_CAPACITY;
@@ -858,6 +871,150 @@ struct Lane {
     }
     return emit(j, m);
   }
+  // ---------------------------------------------------------------- snapshots
+  // Everything here runs only with snapshots on (gr_set_snapshots): off, the
+  // callers escalate as they always did. -DGR_SNAP_OUTLINE=1 (A/B builds) keeps
+  // the two handlers out of line; the lane then lives in memory for them
+  // (Snapshots, has both builds' resource remarks).
+#ifndef GR_SNAP_OUTLINE
+#define GR_SNAP_OUTLINE 0
+#endif
+#if GR_SNAP_OUTLINE
+#define GR_SNAP_FN __host__ __device__ __attribute__((noinline))
+#else
+#define GR_SNAP_FN GR_HD
+#endif
+  GR_HD bool snapshots() const { return GR_SNAPSHOTS_FORCE || kp.snapshots; }
+  GR_HD gr_snapshot_rec* snap_recs() const {
+#if GR_SNAPSHOTS_FORCE && !defined(__HIP_DEVICE_COMPILE__)
+    if (!kp.snap_rec) return snap_host_hook.snap_rec;
+#endif
+    return kp.snap_rec;
+  }
+  GR_HD gr_snapshot_rec* rest_stage() const {  // this peer's kRestStage staging records
+#if GR_SNAPSHOTS_FORCE && !defined(__HIP_DEVICE_COMPILE__)
+    if (!kp.rest_stage) return snap_host_hook.rest_stage ? snap_host_hook.rest_stage + (size_t)p * kRestStage : nullptr;
+#endif
+    return kp.rest_stage ? kp.rest_stage + (size_t)p * kRestStage : nullptr;
+  }
+  // entryLog.snapshot() (logentry.go:238-243): the snapshot a restore of this
+  // pass left in memory, else the group's record.
+  GR_HD void cur_snapshot(uint64_t* idx, uint64_t* t) const {
+    const gr_snapshot_rec* sr = nrest ? rest_stage() + (nrest - 1) : snap_recs() ? snap_recs() + p : nullptr;
+    *idx = sr ? sr->index : 0;
+    *t = sr ? sr->term : 0;
+  }
+  // sendReplicateMessage's ErrCompacted branch (raft.go:514-523) with
+  // makeInstallSnapshotMessage (:463-472) and remote.becomeSnapshot
+  // (remote.go:98-102): m becomes the message send_replicate emits in place of
+  // its Replicate (0), or there is nothing to send (-1), or an escalation.
+  GR_SNAP_FN int snapshot_message(uint32_t j, OutMsg& m) {
+    if (!ractive(j)) {
+      GR_COVER_S(SEND_INACTIVE);
+      return -1;
+    }
+    m.type = GR_INSTALL_SNAPSHOT;
+    m.commit = 0;
+    cur_snapshot(&m.log_index, &m.log_term);  // gpuraft.h: Snapshot.Index / Snapshot.Term
+    if (m.log_index == 0) {
+      GR_COVER_S(SEND_EMPTY_SNAPSHOT);
+      return GR_ESC_PANIC;  // "got an empty snapshot"
+    }
+    GR_COVER_S(SEND_INSTALL);
+    need(G_SNAP);
+    put(snap, j, m.log_index);
+    set_rstate(j, GR_SNAPSHOT_ST);
+    dirty |= D_SNAP | D_REM;
+    return 0;
+  }
+  // handleInstallSnapshotMessage (raft.go:933-951) with raft.restore (:303-325),
+  // entryLog.restore (logentry.go:376-381) and inMemory.restore (inmemory.go:179-184).
+  GR_SNAP_FN int install_snapshot(const InMsg& m, uint32_t from) {
+    need(G_CORE | G_WIN);
+    const uint64_t idx = m.log_index, st = m.log_term;
+    bool restored = false;
+    if (idx <= committed) {
+      GR_COVER_S(IGNORED_COMMITTED);
+    } else {
+      if ((m.flags & MFL_REJECT) && state != GR_OBSERVER) {
+        GR_COVER_S(REJECT_PANIC);
+        return GR_ESC_PANIC;  // "converting to observer"
+      }
+      uint64_t lt;
+      GR_TRY(term_of(idx, &lt));
+      if (lt == st) {  // matchTerm: commitTo (logentry.go:314-323)
+        GR_COVER_S(MATCH_COMMIT);
+        if (idx > hi) return GR_ESC_PANIC;
+        committed = idx;
+        dirty |= D_COMMITTED;
+      } else {
+        gr_snapshot_rec* stage = rest_stage();
+        if (!stage) return GR_ESC_UNSUPPORTED;
+        if (nrest >= kRestStage) return GR_ESC_CAPACITY;  // the staging records are full until the pass stands
+        GR_COVER_S(RESTORE);
+        need(G_INMEM);
+        hi = idx;
+        committed = idx;
+        lo = idx;
+        imk = idx + 1;
+        isv = idx;
+        nruns = 1;
+#pragma unroll
+        for (int r = 0; r < GR_K; ++r) {
+          rs[r] = r == 0 ? idx : 0;
+          rt[r] = r == 0 ? st : 0;
+        }
+        dirty |= D_HI | D_COMMITTED | D_WIN | D_INMEM | D_RESTORE;
+        stage[nrest].index = idx;
+        stage[nrest].term = st;
+        nrest++;
+        restored = true;
+      }
+    }
+    OutMsg r;
+    r.type = GR_REPLICATE_RESP;
+    r.log_index = restored ? hi : committed;
+    return emit(from, r);
+  }
+  // This pass's restores, for gr_restored_snapshots, and the snapshot record.
+  GR_HD void report_restores() {
+    gr_snapshot_rec* sr = snap_recs();
+    const gr_snapshot_rec* stage = rest_stage();
+    uint32_t* hdr = kp.rest_hdr;
+    gr_restored* list = kp.rest;
+    uint32_t cap = kp.rest_cap;
+#if GR_SNAPSHOTS_FORCE && !defined(__HIP_DEVICE_COMPILE__)
+    if (!hdr) {
+      hdr = snap_host_hook.rest_hdr;
+      list = snap_host_hook.rest;
+      cap = snap_host_hook.rest_cap;
+    }
+#endif
+#pragma unroll 1
+    for (uint32_t x = 0; x < nrest && x < kRestStage; ++x) {
+      gr_restored r;
+      r.peer = p;
+      r.pad = 0;
+      r.index = stage[x].index;
+      r.term = stage[x].term;
+      if (sr && x + 1 == nrest) {
+        sr[p].index = r.index;
+        sr[p].term = r.term;
+      }
+      if (!hdr) continue;
+#if defined(__HIP_DEVICE_COMPILE__)
+      const uint32_t at = atomicAdd(hdr, 1u);
+#else
+      const uint32_t at = hdr[0]++;
+#endif
+      if (at >= cap) {
+        hdr[1] = 1;  // sticky: the host reports GR_ECAPACITY
+        continue;
+      }
+      list[at] = r;
+    }
+  }
+
   GR_HD int broadcast_replicate() {  // raft.go:534-546
     need(G_CORE | G_REM);
 #pragma unroll 1
@@ -1656,6 +1813,12 @@ struct Lane {
         default: GR_COVER(L_NIL); return 0;  // nil handler
       }
     }
+    // handleCandidateInstallSnapshot (raft.go:1439-1442) is becomeFollower(term,
+    // From) and then what the follower's handler does, which runs below
+    if (state == GR_CANDIDATE && t == GR_INSTALL_SNAPSHOT && snapshots() && elections()) {
+      GR_COVER_S(C_INSTALL);
+      GR_TRY(become_follower(term, remote_id(from)));
+    }
     if (state == GR_FOLLOWER || state == GR_OBSERVER) {
       const bool obs = state == GR_OBSERVER;
       switch (t) {
@@ -1700,7 +1863,14 @@ struct Lane {
           bool d;
           return forward_to_leader(as_out(m), &d);
         }
-        case GR_INSTALL_SNAPSHOT: return GR_ESC_UNSUPPORTED;
+        case GR_INSTALL_SNAPSHOT:  // handleFollowerInstallSnapshot, raft.go:1401-1405 (observer :1326-1328)
+          need(G_REM);
+          if (!snapshots() || rkind(from) == GR_SLOT_EMPTY) return GR_ESC_UNSUPPORTED;
+          if (obs) GR_COVER_S(O_INSTALL);
+          else GR_COVER_S(F_INSTALL);
+          zero_etick();
+          set_leader_from(from);
+          return install_snapshot(m, from);
         case GR_REQUEST_VOTE:
         case GR_TIMEOUT_NOW:
           if (obs) { GR_COVER(O_DROPPED); return 0; }
@@ -1711,7 +1881,7 @@ struct Lane {
     }
     switch (t) {  // candidate: every non-nil handler changes role or votes
       case GR_PROPOSE: GR_COVER(C_PROPOSE); return 0;  // handleCandidatePropose only logs
-      case GR_INSTALL_SNAPSHOT: return GR_ESC_UNSUPPORTED;
+      case GR_INSTALL_SNAPSHOT: return GR_ESC_UNSUPPORTED;  // snapshots or elections off
       case GR_HEARTBEAT:
       case GR_REPLICATE:
       case GR_REQUEST_VOTE_RESP:
@@ -1814,6 +1984,7 @@ struct Lane {
     outcnt = 0;
     promoted = false;
     transfer_target = false;
+    nrest = 0;
   }
   // This pass's promotion, for gr_promotions: one record, one returning atomic.
   GR_HD void report_promotion() {
@@ -1990,6 +2161,7 @@ struct Lane {
     }
     store();
     if (promoted) report_promotion();  // of the run that stands (a re-run prefix included)
+    if (nrest) report_restores();
     tclk[2] = lane_clock(kp);
 #pragma unroll 1
     for (uint32_t j = 0; j < (uint32_t)S; ++j) {  // every routed mailbox is rewritten each pass

@@ -668,11 +668,44 @@ struct StepParams {
   QuiesceRec* qprev;
   const uint32_t* qcfg;
   const uint32_t* qraw;
+  // snapshots on the device (gr_set_snapshots): wave-uniform, tested only where
+  // the general lane would otherwise escalate (gr_lane.h Lane::snapshots).
+  // snap_rec: the groups' latest snapshots by engine slot (gr_set_snapshot_recs;
+  // a restore writes its own). The restored list (gr_restored_snapshots) as the
+  // promotion list: rest_hdr[0] counts the records appended, rest_hdr[1] is set
+  // when one found the list full (rest_cap: kRestStage records per engine slot,
+  // what one pass can append); nullptr: restores leave no record.
+  // rest_stage: kRestStage records per engine slot where a lane keeps the
+  // restores of its pass until the pass stands (it alone reads and writes them).
+  uint8_t snapshots;
+  uint32_t rest_cap;
+  gr_snapshot_rec* snap_rec;
+  gr_snapshot_rec* rest_stage;
+  uint32_t* rest_hdr;
+  gr_restored* rest;
 };
 // -DGR_ELECTIONS_FORCE=1: elections on whatever StepParams::elections says (the
 // test-only host lane's second build, whose harness zeroes its StepParams).
 #ifndef GR_ELECTIONS_FORCE
 #define GR_ELECTIONS_FORCE 0
+#endif
+// restores one lane can make in one pass (gpuraft.h: the next one escalates)
+constexpr uint32_t kRestStage = 2;
+// -DGR_SNAPSHOTS_FORCE=1: the same for StepParams::snapshots. That harness also
+// leaves the side arrays null, so a host build takes them from snap_host_hook,
+// which its snapshot entry point fills (tests/native/hostlane_snap.hip).
+#ifndef GR_SNAPSHOTS_FORCE
+#define GR_SNAPSHOTS_FORCE 0
+#endif
+#if GR_SNAPSHOTS_FORCE && !defined(__HIP_DEVICE_COMPILE__)
+struct SnapHostHook {
+  gr_snapshot_rec* snap_rec;    // by engine slot
+  gr_snapshot_rec* rest_stage;  // kRestStage per engine slot
+  uint32_t* rest_hdr;
+  gr_restored* rest;
+  uint32_t rest_cap;
+};
+inline SnapHostHook snap_host_hook = {nullptr, nullptr, nullptr, nullptr, 0};
 #endif
 // A tick-list entry's staged inputs (round 5): the fields the steady kernel
 // loads for every lane of a wave that is not steady (coalesced: the wave's

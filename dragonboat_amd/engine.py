@@ -128,6 +128,16 @@ def load_library(path=LIB_PATH):
         lib.gr_set_elections.argtypes = [c.c_void_p, c.c_int]
         lib.gr_get_elections.argtypes = [c.c_void_p]
         lib.gr_promotions.argtypes = [c.c_void_p, c.c_void_p, c.c_size_t, c.POINTER(c.c_size_t)]
+    if hasattr(lib, "gr_coverage_snap_read"):
+        lib.gr_coverage_snap_read.argtypes = [c.c_void_p, c.c_uint32]
+        lib.gr_coverage_snap_names.restype = c.c_char_p
+    if hasattr(lib, "gr_set_snapshots"):  # (older builds loaded for A/B runs lack snapshots)
+        lib.gr_set_snapshots.argtypes = [c.c_void_p, c.c_int]
+        lib.gr_get_snapshots.argtypes = [c.c_void_p]
+        lib.gr_set_snapshot_recs.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t]
+        lib.gr_get_snapshot_recs.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t]
+        lib.gr_restored_snapshots.argtypes = [c.c_void_p, c.c_void_p, c.c_size_t, c.POINTER(c.c_size_t)]
+        lib.gr_restore_remotes.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p]
     if hasattr(lib, "gr_set_quiesce"):  # (older builds loaded for A/B runs lack the quiesce manager)
         lib.gr_set_quiesce.argtypes = [c.c_void_p, c.c_int]
         lib.gr_get_quiesce.argtypes = [c.c_void_p]
@@ -155,8 +165,10 @@ class Engine:
     """One engine = one device's slab of group slots (engine slots 0..max_peers-1)."""
 
     def __init__(self, max_peers, slots=3, device=0, max_entry_size=abi.MAX_ENTRY_SIZE, lib_path=None,
-                 elections=False, quiesce=False):
-        """elections: run elections on the device (gr_set_elections); False leaves
+                 elections=False, quiesce=False, snapshots=False):
+        """snapshots: send and restore snapshots on the device (gr_set_snapshots);
+        False leaves the default, which GR_SNAPSHOTS=1 turns on.
+        elections: run elections on the device (gr_set_elections); False leaves
         the engine's default, which GR_ELECTIONS=1 in the environment turns on.
         quiesce: run the quiesce manager on the device (gr_set_quiesce); False
         leaves the default, which GR_QUIESCE_ON_DEVICE=1 turns on."""
@@ -174,6 +186,57 @@ class Engine:
             self.set_elections(True)
         if quiesce:
             self.set_quiesce(True)
+        if snapshots:
+            self.set_snapshots(True)
+
+    def set_snapshots(self, on):
+        """InstallSnapshot sends and restores on the device (gpuraft.h gr_set_snapshots)."""
+        _check(self.lib.gr_set_snapshots(self._h, 1 if on else 0), "gr_set_snapshots")
+
+    def get_snapshots(self):
+        return bool(self.lib.gr_get_snapshots(self._h))
+
+    def set_snapshot_recs(self, slots, recs):
+        """The groups' latest snapshots (abi.SNAPSHOT_REC) for a list of engine
+        slots (gr_set_snapshot_recs): call it after LogReader.CreateSnapshot."""
+        slots = np.ascontiguousarray(slots, np.uint32)
+        recs = np.ascontiguousarray(recs, abi.SNAPSHOT_REC)
+        assert len(slots) == len(recs)
+        _check(self.lib.gr_set_snapshot_recs(self._h, slots.ctypes.data if len(slots) else None,
+                                             recs.ctypes.data if len(recs) else None, len(slots)),
+               "gr_set_snapshot_recs")
+
+    def get_snapshot_recs(self, slots):
+        slots = np.ascontiguousarray(slots, np.uint32)
+        out = np.zeros(len(slots), abi.SNAPSHOT_REC)
+        _check(self.lib.gr_get_snapshot_recs(self._h, slots.ctypes.data if len(slots) else None,
+                                             out.ctypes.data if len(out) else None, len(slots)),
+               "gr_get_snapshot_recs")
+        return out
+
+    def restored_snapshots(self):
+        """Drain the restored list: abi.RESTORED records (peer, index, term) of
+        every snapshot restored on the device since the last call."""
+        out = np.zeros(2 * self.max_peers, abi.RESTORED)  # a peer restores at most twice per pass
+        n = ctypes.c_size_t()
+        _check(self.lib.gr_restored_snapshots(self._h, out.ctypes.data, len(out), ctypes.byref(n)),
+               "gr_restored_snapshots")
+        return out[:n.value].copy()
+
+    def restore_remotes(self, slots, ms):
+        """Peer.RestoreRemotes on the device (gr_restore_remotes): ms is an
+        abi.MEMBERSHIP array, one record per listed engine slot. Returns (rc,
+        per-slot status) as apply_config_change does, and raises as it does."""
+        slots = np.ascontiguousarray(slots, np.uint32)
+        ms = np.ascontiguousarray(ms, abi.MEMBERSHIP)
+        assert len(slots) == len(ms)
+        st = np.full(len(slots), -1, np.int32)  # no gr_cc_status: still there after a refused call
+        rc = self.lib.gr_restore_remotes(self._h, slots.ctypes.data if len(slots) else None,
+                                         ms.ctypes.data if len(ms) else None, len(slots),
+                                         st.ctypes.data if len(st) else None)
+        if rc not in (0, -6) or (rc == -6 and st[0] < 0):
+            _check(rc, "gr_restore_remotes")
+        return rc, st
 
     def set_elections(self, on):
         """Campaigns, votes and promotions on the device (gpuraft.h gr_set_elections)."""

@@ -72,7 +72,8 @@ enum gr_escalation {
   GR_ESC_NONE = 0,
   GR_ESC_TERM_WINDOW = 1,    /* term lookup below the device term window (LogReader.Term path) */
   GR_ESC_RANDOM = 2,         /* a second reset() in one pass needs another random draw */
-  /* message/state pair handled by the host: snapshots; with elections off
+  /* message/state pair handled by the host: a received InstallSnapshot with
+   * snapshots off (gr_set_snapshots; on, see there for what is left); with elections off
    * (gr_set_elections) also votes, TimeoutNow and every candidate handler; with
    * elections on, a RequestVoteResp that would promote a candidate whose log
    * has uncommitted entries (committed < last_index), and a RequestVote from a
@@ -85,7 +86,7 @@ enum gr_escalation {
   GR_ESC_ELECTION = 4,
   GR_ESC_PANIC = 5,          /* the reference would panic on this item */
   GR_ESC_CAPACITY = 6,       /* mailbox / ReadIndex FIFO / ReadyToRead capacity */
-  GR_ESC_SNAPSHOT = 7,       /* Replicate needs entries below firstIndex: InstallSnapshot path */
+  GR_ESC_SNAPSHOT = 7,       /* Replicate needs entries below firstIndex: InstallSnapshot path (snapshots off) */
   GR_ESC_ENTRY_SIZE = 8,     /* settings.Soft.MaxEntrySize may bind (raft.go:513) */
   GR_ESC_MSG_RUNS = 9,       /* Replicate entries span more than 2 term runs */
   GR_ESC_NONMEMBER = 10,     /* target node id has no remote slot */
@@ -490,7 +491,8 @@ int gr_step_compact(gr_engine* e, const gr_cinbox* in, gr_coutbox* out);
  * pending pass owns the engine's scratch and lane rows: every other call on
  * that engine that steps it or uses them (gr_step, gr_step_compact{,_begin},
  * gr_step_device, gr_load_* / gr_sync_*, gr_set_locals, gr_bind_routes,
- * gr_compact_log, gr_commit_update, gr_apply_config_change, gr_notify_applied, gr_collect_results,
+ * gr_compact_log, gr_commit_update, gr_apply_config_change, gr_restore_remotes, gr_notify_applied,
+ * gr_set_snapshot_recs, gr_get_snapshot_recs, gr_restored_snapshots, gr_collect_results,
  * gr_space_cold_used) returns GR_ESTATE and changes nothing. */
 int gr_step_compact_begin(gr_engine* e, const gr_cinbox* in);
 int gr_step_compact_end(gr_engine* e, gr_coutbox* out);
@@ -678,6 +680,104 @@ typedef struct gr_promotion {
   uint64_t noop_index; /* last_index after the promotion's empty entry */
 } gr_promotion;
 int gr_promotions(gr_engine* e, gr_promotion* out, size_t cap, size_t* n);
+/*
+ * Snapshots on the device (off by default; GR_SNAPSHOTS=1 in the environment at
+ * gr_create turns them on). Off, a leader whose send would start at or below
+ * firstIndex - 1 escalates GR_ESC_SNAPSHOT and every received InstallSnapshot
+ * escalates GR_ESC_UNSUPPORTED, as ever; every result, record and escalation is
+ * what it was without this section. On, the general lane runs the
+ * InstallSnapshot branch of sendReplicateMessage (raft.go:500-532 with
+ * makeInstallSnapshotMessage :463-472 and remote.becomeSnapshot,
+ * remote.go:98-102) and handleInstallSnapshotMessage with raft.restore
+ * (raft.go:303-325, 933-951) for followers and observers (:1401-1405,
+ * :1326-1328) and, with elections on too, candidates (:1439-1442). The switch
+ * applies to passes launched after the call; a captured graph keeps the setting
+ * it was captured with. gr_get_snapshots: 0 or 1 (GR_EINVAL for a NULL engine).
+ *
+ * The snapshot record is the group's latest snapshot as entryLog.snapshot()
+ * returns it (logentry.go:238-243): the one a restore left in memory, else
+ * LogReader's. index 0 is the empty snapshot. The records live in an array of
+ * their own, one 16-byte record per engine slot, zeroed at gr_create (beside it
+ * the engine keeps two staging records per slot for the restores of a pass in
+ * flight); gr_load_* and gr_sync_* of a group do not touch them. The host calls gr_set_snapshot_recs after
+ * LogReader.CreateSnapshot; a restore on the device writes the record itself.
+ * Records are taken as given. Slots out of range or listed twice: GR_ERANGE
+ * before anything is written (as gr_notify_applied).
+ *
+ * Message convention: a gr_message of type GR_INSTALL_SNAPSHOT carries
+ * Snapshot.Index in log_index and Snapshot.Term in log_term; commit is 0 (the
+ * reference message has LogIndex = LogTerm = Commit = 0: a binding fills
+ * pb.Snapshot from its LogReader and zeroes those fields on the way out, and
+ * does the reverse on the way in). On an inbound record reject = 1 means that
+ * the receiver's node id is in Snapshot.Membership.Observers; the host resolves
+ * it, as it resolves From into a slot. The message always travels as a full
+ * record: an ext record in the compact formats, a cold record in mailboxes.
+ * gr_step_wire keeps returning GR_WIRE_SNAPSHOT for a frame that carries a
+ * Snapshot. Payloads, chunks and their transport stay on the host.
+ *
+ * What still escalates with the switch on: an empty snapshot record on a leader
+ * that has to send one (GR_ESC_PANIC, "got an empty snapshot"); reject on a peer
+ * that is no observer (GR_ESC_PANIC, "converting to observer"); a matchTerm
+ * lookup below the term-run window (GR_ESC_TERM_WINDOW); a third restore in one
+ * pass (GR_ESC_CAPACITY: a lane holds two until its pass stands); an
+ * InstallSnapshot from a slot that is not a member, and one that reaches a
+ * candidate with elections off (GR_ESC_UNSUPPORTED).
+ *
+ * A restore (raft.restore returned true) makes last_index, committed,
+ * first_index_m1, saved_to and log_applied the snapshot's index, marker_index
+ * index + 1, and the term-run window the single run (index, term); raft.applied
+ * and the remotes stay. The pass's pb.Update then carries the Snapshot
+ * (peer.go:311-337), which no result field announces: every restore leaves one
+ * gr_restored record, drained by gr_restored_snapshots under gr_promotions'
+ * rules (the call waits for the device, copies at most `cap` records, empties
+ * the list; the list holds 2 * max_peers records, what one pass can append; a
+ * restore that finds it full is lost and every later call returns GR_ECAPACITY, as does a call whose `cap` is
+ * below the number pending, which drains nothing). The records and the snapshot
+ * record belong to the run that stands: an escalated peer's reflect exactly the
+ * items below esc_item.
+ */
+int gr_set_snapshots(gr_engine* e, int on);
+int gr_get_snapshots(const gr_engine* e);
+typedef struct gr_snapshot_rec {
+  uint64_t index, term;
+} gr_snapshot_rec;
+int gr_set_snapshot_recs(gr_engine* e, const uint32_t* slots, const gr_snapshot_rec* recs, size_t n);
+int gr_get_snapshot_recs(gr_engine* e, const uint32_t* slots, gr_snapshot_rec* out, size_t n);
+typedef struct gr_restored {
+  uint32_t peer; /* engine slot */
+  uint32_t pad;
+  uint64_t index, term; /* the restored Snapshot.Index / Snapshot.Term */
+} gr_restored;
+int gr_restored_snapshots(gr_engine* e, gr_restored* out, size_t cap, size_t* n);
+/*
+ * Peer.RestoreRemotes(ss) (peer.go:177-180 -> raft.restoreRemotes,
+ * raft.go:327-355) for a list of engine slots: the host calls it once the RSM has
+ * recovered from a snapshot, with the snapshot's membership (the 80-byte record
+ * and the 4-byte slot go up, a 4-byte status comes down; the state stays on the
+ * device). ms[x] lists the members:
+ * node_id[k] with kind[k] GR_SLOT_VOTER (Membership.Addresses) or
+ * GR_SLOT_OBSERVER (Membership.Observers); the first GR_SLOT_EMPTY kind ends the
+ * list. Every listed id gets a fresh remote (match 0, or last_index for the peer
+ * itself; next last_index + 1; Retry, inactive, snapshot_index 0); a member not
+ * listed becomes GR_SLOT_EMPTY and its slot keeps its id. If a listed voter was
+ * an observer on this peer, whichever id it is, the reference runs
+ * becomeFollower(term, leaderID) (raft.go:329-333) with `rand` as reset()'s draw.
+ * An id keeps the slot that already carries it (live, or empty with that id), so
+ * mailbox routes stay valid; other ids take free slots by
+ * gr_apply_config_change's rule, the ReadIndex ack restriction included.
+ * status[x] is a gr_cc_status: GR_CC_HOST for a candidate, for more than one
+ * observer-to-voter id (each needs a draw), for a promoted peer without an
+ * election timeout, for an id listed twice; GR_CC_NO_SLOT when the ids do not
+ * fit. A refused peer is left untouched, bit for bit. Call it between passes;
+ * return values, slot rules and the refusal while a gr_step_compact_begin is
+ * pending are gr_apply_config_change's.
+ */
+typedef struct gr_membership {
+  uint64_t node_id[GR_SMAX];
+  uint8_t kind[GR_SMAX]; /* gr_slot_kind */
+  uint64_t rand;         /* as gr_config_change.rand */
+} gr_membership;
+int gr_restore_remotes(gr_engine* e, const uint32_t* slots, const gr_membership* ms, size_t n, int32_t* status);
 /*
  * The quiesce manager on the device (off by default; GR_QUIESCE_ON_DEVICE=1 in
  * the environment at gr_create turns it on). In the reference every node owns a
