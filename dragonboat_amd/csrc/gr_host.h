@@ -373,6 +373,7 @@ __host__ __device__ inline void derive_proposals(gr_peer_result* pr, uint8_t rf,
                              uint32_t local_n, uint8_t fwd_n, uint32_t fwd_entries) {
   uint64_t n = 0;
   if (rf & RF_PROPOSE) {
+    if (rf & RF_PROP_OK) pres = GR_PROP_APPENDED;  // the row was not written (gr_layout.h)
     pr->propose_result = pres;
     if (pres == GR_PROP_APPENDED) n += local_n;
   }
@@ -399,7 +400,8 @@ __host__ __device__ inline gr_peer_result make_result(const LaneBase& L, const S
   if (rf & (RF_PROPOSE | RF_FORWARDED))
     derive_proposals(&pr, rf, L.u8(LR_PROP_RESULT)[l], pr.last_index, L.u32(LR_PROPOSE)[l], L.u8(LR_FWD_COUNT)[l],
                      L.u32(LR_FWD_ENTRIES)[l]);
-  if (rf & RF_APPEND) pr.append_from = L.u64(LR_APPEND_FROM)[l];
+  // RF_APPEND_LAST: the row was not written, the one entry is the last (gr_layout.h)
+  if (rf & RF_APPEND) pr.append_from = (rf & RF_APPEND_LAST) ? pr.last_index : L.u64(LR_APPEND_FROM)[l];
   if (rf & RF_READY) {
     pr.n_ready = L.u8(LR_RTR_COUNT)[l];
     for (int q = 0; q < GR_Q; ++q) {

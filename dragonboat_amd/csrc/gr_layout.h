@@ -345,6 +345,16 @@ constexpr uint8_t RF_READY = 0x04;
 constexpr uint8_t RF_APPEND = 0x08;
 constexpr uint8_t RF_FORWARDED = 0x10;  // forwarded Propose batches appended: LR_FWD_COUNT, LR_FWD_ENTRIES
 constexpr uint8_t RF_HARDSTATE = 0x20;  // term or vote changed (pb.Update.State differs)
+// Result rows that follow from the flags: only the steady lanes (gr_steady.h) set
+// these bits, and then do not write the row; every other lane writes the rows and
+// leaves the bits clear. host::make_result and derive_proposals resolve them.
+//   RF_APPEND_LAST (with RF_APPEND): append_from is the peer's lastIndex after
+//   the pass (one entry appended, the last one: every steady pass), and
+//   LR_APPEND_FROM was not written;
+//   RF_PROP_OK (with RF_PROPOSE): the result is GR_PROP_APPENDED, and
+//   LR_PROP_RESULT was not written.
+constexpr uint8_t RF_APPEND_LAST = 0x40;
+constexpr uint8_t RF_PROP_OK = 0x80;
 
 // ---------------------------------------------------------------- message spaces
 enum U64Field : uint32_t { MF_LOG_INDEX = 0, MF_COMMIT = 1, MF_HINT = 2, MF_HINT_HIGH = 3, MF_NUM_U64 = 4 };

@@ -380,8 +380,8 @@ struct SteadyLeader : SteadyBase<A> {
       ntst(mb.mterm(), (uint32_t)term);
       ntst(mb.cnt(), (uint8_t)nb);
     }
-    if (np) a.prop_result() = (uint8_t)GR_PROP_APPENDED;
-    ntst(a.rflags(), (uint8_t)(np ? RF_PROPOSE : 0));
+    // the result is GR_PROP_APPENDED: RF_PROP_OK says so, no LR_PROP_RESULT store
+    ntst(a.rflags(), (uint8_t)(np ? RF_PROPOSE | RF_PROP_OK : 0));
     const uint32_t nmo = nout * (S - 1);
     ls->leader_commit = c > committed0;
     ls->follower_commit = 0;
@@ -497,8 +497,11 @@ struct SteadyFollower : SteadyBase<A> {
       ntst(mo.mterm(), (uint32_t)term);
       ntst(mo.cnt(), (uint8_t)(c | MB_UNIFORM | MB_RESP | (shared ? MB_SHARED : 0u)));
     }
-    if (append_from) a.append_from() = append_from;
-    ntst(a.rflags(), (uint8_t)(append_from ? RF_APPEND : 0));
+    // one append and it is the last index (every steady pass): RF_APPEND_LAST
+    // says so and the row is not stored
+    const bool app_last = append_from == hi;
+    if (append_from && !app_last) a.append_from() = append_from;
+    ntst(a.rflags(), (uint8_t)(append_from ? (app_last ? RF_APPEND | RF_APPEND_LAST : RF_APPEND) : 0));
     ls->leader_commit = 0;
     ls->follower_commit = committed > committed0;
     ls->escalated = 0;
