@@ -115,6 +115,9 @@ RESTORED = np.dtype([("peer", u32), ("pad", u32), ("index", u64), ("term", u64)]
 assert RESTORED.itemsize == 24
 MEMBERSHIP = np.dtype([("node_id", u64, (GR_SMAX,)), ("kind", u8, (GR_SMAX,)), ("rand", u64)])
 assert MEMBERSHIP.itemsize == 80
+# gr_cc_index (gpuraft.h, config-change entries on the device)
+CC_INDEX = np.dtype([("last", u64), ("prev", u64)])
+assert CC_INDEX.itemsize == 16
 SIZES = {"gr_peer": 664, "gr_message": 80, "gr_local_input": 48, "gr_peer_result": 168,
          "gr_remote": 32, "gr_read_status": 32}
 assert PEER.itemsize == SIZES["gr_peer"], PEER.itemsize
@@ -203,6 +206,7 @@ EXPORTS = [
     "gr_set_elections", "gr_get_elections", "gr_promotions",
     "gr_set_snapshots", "gr_get_snapshots", "gr_set_snapshot_recs", "gr_get_snapshot_recs", "gr_restored_snapshots",
     "gr_restore_remotes",
+    "gr_set_config_entries", "gr_get_config_entries", "gr_set_cc_indexes", "gr_get_cc_indexes",
     "gr_set_quiesce", "gr_get_quiesce", "gr_load_quiesce", "gr_sync_quiesce", "gr_load_quiesce_peers",
     "gr_sync_quiesce_peers", "gr_tick_all", "gr_splitmix64",
 ]

@@ -6,6 +6,8 @@
 - libconfig_change_host.so: gr_config_change.h for the host and its reference side, test-only.
 - libhostlane_snap.so, libhostlane_snap_elect.so: the host lane with snapshots compiled on and
   their reference side, test-only.
+- libhostlane_cc.so, libhostlane_cc_elect.so: the host lane with config-change entries compiled
+  on and their reference side, test-only.
 Outputs stay in-tree (git-ignored) so they travel to the GPU box.
 """
 import os
@@ -35,6 +37,8 @@ STEADY_WU_HOST_LIB = os.path.join(ROOT, "tests", "_build", "libsteady_wu_host.so
 CONFIG_CHANGE_HOST_LIB = os.path.join(ROOT, "tests", "_build", "libconfig_change_host.so")
 HOSTLANE_SNAP_LIB = os.path.join(ROOT, "tests", "_build", "libhostlane_snap.so")
 HOSTLANE_SNAP_ELECT_LIB = os.path.join(ROOT, "tests", "_build", "libhostlane_snap_elect.so")
+HOSTLANE_CC_LIB = os.path.join(ROOT, "tests", "_build", "libhostlane_cc.so")
+HOSTLANE_CC_ELECT_LIB = os.path.join(ROOT, "tests", "_build", "libhostlane_cc_elect.so")
 WIRE_SRC = os.path.join(ROOT, "dragonboat_amd", "csrc", "gr_wire.hip")
 WIRE_DEPS = [WIRE_SRC, os.path.join(ROOT, "include", "gpuraft_wire.h"), os.path.join(ROOT, "include", "gpuraft.h"),
              os.path.join(CSRC, "gr_scan.h")]
@@ -349,6 +353,40 @@ def build_hostlane_snap_elect(force=False):
     return build_hostlane_snap(force, HOSTLANE_SNAP_ELECT_LIB, ("-DGR_ELECTIONS_FORCE=1",))
 
 
+def build_hostlane_cc(force=False, out=HOSTLANE_CC_LIB, extra=()):
+    """libhostlane_cc.so: the host lane with config-change entries compiled on
+    (tests/native/hostlane_cc.hip, -DGR_CONFIG_ENTRIES_FORCE=1: its harness zeroes
+    StepParams, so the run-time switch cannot reach it) and the reference side
+    (tests/native/config_entries_ref.cpp, the oracle's raft object with typed
+    in-memory entries), for tests/test_config_entries.py."""
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    odir = os.path.join(ROOT, "oracle")
+    src = os.path.join(ROOT, "tests", "native", "hostlane_cc.hip")
+    ref = os.path.join(ROOT, "tests", "native", "config_entries_ref.cpp")
+    deps = ENGINE_DEPS + [src, ref, os.path.join(ROOT, "tests", "native", "hostlane.hip"),
+                          os.path.join(odir, "batch.cpp"), os.path.join(odir, "raft_oracle.hpp")]
+    if not (force or _stale(out, deps)):
+        return out
+    with _locked(out):
+        if force or _stale(out, deps):
+            inc = ["-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-I" + odir]
+            objs = [out + ".host.o", out + ".ref.o"]
+            with ThreadPoolExecutor(2) as ex:
+                fs = [ex.submit(_run, [HIPCC, "--cuda-host-only", "-O2", "-g", "-std=c++17", "-fPIC", "-DGR_COVERAGE",
+                                       "-DGR_CONFIG_ENTRIES_FORCE=1", *extra, *inc, "-c", src, "-o", objs[0]]),
+                      ex.submit(_run, ["g++", "-std=c++17", "-O2", "-g", "-fPIC", *inc, "-c", ref, "-o", objs[1]])]
+                for f in fs:
+                    f.result()
+            _run([HIPCC, "-shared", "-fPIC", *objs, "-o", out, "-lpthread"])
+    return out
+
+
+def build_hostlane_cc_elect(force=False):
+    """libhostlane_cc_elect.so: the same with elections compiled on too, for
+    promotions over uncommitted entries."""
+    return build_hostlane_cc(force, HOSTLANE_CC_ELECT_LIB, ("-DGR_ELECTIONS_FORCE=1",))
+
+
 ORACLE_SAN_LIB = os.path.join(ROOT, "oracle", "_build", "liboracle_san.so")
 KAT_SAN_BIN = os.path.join(ROOT, "oracle", "_build", "kat_tests_san")
 HOSTLANE_SAN_LIB = os.path.join(ROOT, "tests", "_build", "libhostlane_san.so")
@@ -430,9 +468,10 @@ def build_tools(force=False):
 
 def build_all(force=False):
     # independent targets side by side (each engine build also compiles its units in parallel)
-    with ThreadPoolExecutor(7) as ex:
+    with ThreadPoolExecutor(9) as ex:
         fs = [ex.submit(f, force) for f in (build_engine, build_engine_cover, build_hostlane, build_hostlane_elect, build_wire,
-                                            build_hostlane_snap, build_hostlane_snap_elect)]
+                                            build_hostlane_snap, build_hostlane_snap_elect,
+                                            build_hostlane_cc, build_hostlane_cc_elect)]
         build_oracle(force)
         build_wire_oracle(force)
         build_tools(force)

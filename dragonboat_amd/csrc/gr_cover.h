@@ -86,6 +86,17 @@ enum CoverQuiesceId : uint32_t { GR_COVER_QUIESCE_IDS(GR_COVER_ENUM) CQ_N };
 enum CoverSnapId : uint32_t { GR_COVER_SNAP_IDS(GR_COVER_ENUM) CS_N };
 #undef GR_COVER_ENUM
 
+// The config-change-entry handlers' ids (gr_lane.h with
+// StepParams::config_entries, and the lean leader's hand-over in gr_fast.h): a
+// fifth table, read out through gr_coverage_cc_read, so the others stay as they are.
+#define GR_COVER_CC_IDS(X)                                                                        \
+  X(PROPOSE_LOCAL) X(PROPOSE_FWD) X(PROPOSE_PENDING) X(PROPOSED) X(SEND_MARK) X(SEND_MARK_TWO)       \
+  X(SEND_NO_MARK) X(MERGE) X(TRUNCATE_KEEP) X(TRUNCATE_DROP) X(TRUNCATE_TWO) X(PROMOTE_CLEAR)        \
+  X(PROMOTE_PENDING) X(PROMOTE_PANIC) X(LEAN_HANDOVER)
+#define GR_COVER_ENUM(n) CC_##n,
+enum CoverCcId : uint32_t { GR_COVER_CC_IDS(GR_COVER_ENUM) CC_N };
+#undef GR_COVER_ENUM
+
 #ifdef GR_COVERAGE
 // one array per code object (the kernels of each slot count are their own translation unit)
 static __device__ unsigned long long gr_cover_dev[CV_N];
@@ -120,6 +131,16 @@ __host__ __device__ static inline void cover_snap_hit(uint32_t id) {
 #endif
 }
 #define GR_COVER_S(id) ::gr::cover_snap_hit(::gr::CS_##id)
+static __device__ unsigned long long gr_cover_cc_dev[CC_N];
+inline unsigned long long gr_cover_cc_host[CC_N];
+__host__ __device__ static inline void cover_cc_hit(uint32_t id) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  atomicAdd(&gr_cover_cc_dev[id], 1ull);
+#else
+  gr_cover_cc_host[id]++;
+#endif
+}
+#define GR_COVER_C(id) ::gr::cover_cc_hit(::gr::CC_##id)
 __host__ __device__ static inline void cover_hit(uint32_t id) {
 #if defined(__HIP_DEVICE_COMPILE__)
   atomicAdd(&gr_cover_dev[id], 1ull);
@@ -135,6 +156,7 @@ __host__ __device__ static inline void cover_hit(uint32_t id) {
 #define GR_COVER_E(id) ((void)0)
 #define GR_COVER_Q(id) ((void)0)
 #define GR_COVER_S(id) ((void)0)
+#define GR_COVER_C(id) ((void)0)
 #define GR_COVER_ESC(e) ((void)0)
 #define GR_CHECK_INV(cond, id) ((void)0)
 #endif

@@ -46,6 +46,10 @@ extern template hipError_t cover_snap_read<1>(uint64_t*);
 extern template hipError_t cover_snap_read<3>(uint64_t*);
 extern template hipError_t cover_snap_read<5>(uint64_t*);
 extern template hipError_t cover_snap_read<8>(uint64_t*);
+extern template hipError_t cover_cc_read<1>(uint64_t*);
+extern template hipError_t cover_cc_read<3>(uint64_t*);
+extern template hipError_t cover_cc_read<5>(uint64_t*);
+extern template hipError_t cover_cc_read<8>(uint64_t*);
 #endif
 
 // tick_lanes: launch the tick kernel (some lane may carry ticks or a ReadIndex).
@@ -127,6 +131,10 @@ struct gr_engine {
   // with kRestStage records per engine slot
   gr_snapshot_rec* snap_rec = nullptr;  // max_peers records, then the lanes' staging records (kRestStage each)
   uint8_t* rest = nullptr;
+  uint8_t config_entries = 0;  // StepParams::config_entries (gr_set_config_entries; GR_CONFIG_ENTRIES=1 at gr_create)
+  // the groups' config-change index records (gr_set_cc_indexes): max_peers
+  // records, zeroed, then as many staging records (one per engine slot)
+  gr_cc_index* cc_rec = nullptr;
   // the quiesce manager (gr_set_quiesce; GR_QUIESCE_ON_DEVICE=1 at gr_create):
   // one allocation, made by the first gr_load_quiesce or when the switch first
   // goes on, of cap records (qrec), as many pre-pass records (qprev), the words
@@ -268,6 +276,9 @@ StepParams base_params(gr_engine* e) {
   kp.rest_hdr = (uint32_t*)e->rest;
   kp.rest = (gr_restored*)(e->rest + kPromoHeader);
   kp.rest_cap = kRestStage * e->cfg.max_peers;
+  kp.config_entries = e->config_entries;
+  kp.cc_rec = e->cc_rec;
+  kp.cc_stage = e->cc_rec + e->cfg.max_peers;
   kp.quiesce = e->quiesce;
   kp.qrec = e->qrec;
   kp.qprev = e->qprev;
@@ -477,6 +488,7 @@ int gr_create(const gr_config* cfg, gr_engine** out) {
   if (const char* wu = getenv("GR_STEADY_WU")) e->wu_enabled = !(wu[0] == '0' && wu[1] == 0);
   if (const char* el = getenv("GR_ELECTIONS")) e->elections = el[0] == '1';
   if (const char* sn = getenv("GR_SNAPSHOTS")) e->snapshots = sn[0] == '1';
+  if (const char* ce = getenv("GR_CONFIG_ENTRIES")) e->config_entries = ce[0] == '1';
   const char* qd = getenv("GR_QUIESCE_ON_DEVICE");
   if (const char* wc = getenv("GR_WAVE_CLOCK")) {
     // two regions: the general kernel's waves, then the tick kernel's (gr_kernels.h)
@@ -494,6 +506,7 @@ int gr_create(const gr_config* cfg, gr_engine** out) {
       hipMalloc((void**)&e->promo, kPromoHeader + (size_t)cfg->max_peers * sizeof(gr_promotion)) != hipSuccess ||
       hipMalloc((void**)&e->snap_rec, (size_t)cfg->max_peers * (1 + kRestStage) * sizeof(gr_snapshot_rec)) != hipSuccess ||
       hipMalloc((void**)&e->rest, kPromoHeader + (size_t)kRestStage * cfg->max_peers * sizeof(gr_restored)) != hipSuccess ||
+      hipMalloc((void**)&e->cc_rec, (size_t)cfg->max_peers * 2 * sizeof(gr_cc_index)) != hipSuccess ||
       hipMalloc((void**)&e->hints, 2 * hint_stride(e->cap)) != hipSuccess) {
     if (ds) (void)hipFree(ds);
     if (dl) (void)hipFree(dl);
@@ -511,6 +524,7 @@ int gr_create(const gr_config* cfg, gr_engine** out) {
       hipMemset(e->promo, 0, kPromoHeader) != hipSuccess ||
       hipMemset(e->snap_rec, 0, (size_t)cfg->max_peers * (1 + kRestStage) * sizeof(gr_snapshot_rec)) != hipSuccess ||
       hipMemset(e->rest, 0, kPromoHeader) != hipSuccess ||
+      hipMemset(e->cc_rec, 0, (size_t)cfg->max_peers * 2 * sizeof(gr_cc_index)) != hipSuccess ||
       hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess) {
     gr_destroy(e);
     return GR_EDEVICE;
@@ -546,6 +560,7 @@ void gr_destroy(gr_engine* e) {
   if (e->promo) (void)hipFree(e->promo);
   if (e->snap_rec) (void)hipFree(e->snap_rec);
   if (e->rest) (void)hipFree(e->rest);
+  if (e->cc_rec) (void)hipFree(e->cc_rec);
   if (e->qmem) (void)hipFree(e->qmem);
   if (e->tail_hint) (void)hipHostFree(e->tail_hint);
   if (e->wclock) {
@@ -824,6 +839,51 @@ int gr_set_snapshot_recs(gr_engine* e, const uint32_t* slots, const gr_snapshot_
 }
 int gr_get_snapshot_recs(gr_engine* e, const uint32_t* slots, gr_snapshot_rec* out, size_t n) {
   return transfer_snapshot_recs(e, slots, out, n, false);
+}
+
+// The config-change index records of a slot list (gpuraft.h): a side array, as
+// the snapshot records.
+static int transfer_cc_indexes(gr_engine* e, const uint32_t* slots, gr_cc_index* host, size_t n, bool to_device) {
+  if (!e || (n && (!slots || !host))) return GR_EINVAL;
+  if (n == 0) return GR_OK;
+  if (n >= 0x80000000ull) return GR_EINVAL;
+  const uint32_t cap = e->cfg.max_peers;
+  std::vector<uint64_t> seen((cap + 63) / 64, 0);
+  for (size_t x = 0; x < n; ++x) {
+    const uint32_t p = slots[x];
+    if (p >= cap || (seen[p >> 6] >> (p & 63)) & 1) return GR_ERANGE;  // nothing written
+    seen[p >> 6] |= 1ull << (p & 63);
+  }
+  std::lock_guard<std::mutex> guard(e->mu);
+  GR_REFUSE_PENDING(e);
+  HIPCHK(hipDeviceSynchronize());  // passes in flight on other streams read and write the records
+  const hipStream_t s = e->stream;
+  const size_t bytes = n * sizeof(gr_cc_index);
+  int r;
+  if ((r = grow_device(&e->d_slots.p, &e->d_slots.n, n * 4))) return r;
+  if ((r = grow_device(&e->d_peers.p, &e->d_peers.n, bytes))) return r;
+  gr_cc_index* d = (gr_cc_index*)e->d_peers.p;
+  HIPCHK(hipMemcpyAsync(e->d_slots.p, slots, n * 4, hipMemcpyHostToDevice, s));
+  const dim3 grid(io_grid(n)), blk(io::kIoBlock);
+  if (to_device) {
+    HIPCHK(hipMemcpyAsync(d, host, bytes, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(io::set_cc_indexes, grid, blk, 0, s, e->cc_rec, (const uint32_t*)e->d_slots.p,
+                       (const gr_cc_index*)d, (uint32_t)n);
+    HIPCHK(hipGetLastError());
+  } else {
+    hipLaunchKernelGGL(io::get_cc_indexes, grid, blk, 0, s, (const gr_cc_index*)e->cc_rec,
+                       (const uint32_t*)e->d_slots.p, d, (uint32_t)n);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(host, d, bytes, hipMemcpyDeviceToHost, s));
+  }
+  HIPCHK(hipStreamSynchronize(s));
+  return GR_OK;
+}
+int gr_set_cc_indexes(gr_engine* e, const uint32_t* slots, const gr_cc_index* recs, size_t n) {
+  return transfer_cc_indexes(e, slots, const_cast<gr_cc_index*>(recs), n, true);
+}
+int gr_get_cc_indexes(gr_engine* e, const uint32_t* slots, gr_cc_index* out, size_t n) {
+  return transfer_cc_indexes(e, slots, out, n, false);
 }
 
 // Peer.NotifyRaftLastApplied (peer.go:282-284) for a slot list: raft.applied =
@@ -1176,7 +1236,7 @@ static int step_staged(gr_engine* e, uint32_t nm, const gr_local_input* locals, 
     HIPCHK(hipGetLastError());
   }
   hipLaunchKernelGGL(io::mark_inputs, dim3(io_grid(nm + nlc)), blk, 0, s, dmsgs, nm, dloc, nlc, S, cap, mark,
-                     scal + 1);
+                     scal + 1, (uint32_t)e->config_entries);
   HIPCHK(hipGetLastError());
   if ((r = io_scan(e, mark, lop, cap, s))) return r;
   hipLaunchKernelGGL(io::finish_lanes, dim3(1), dim3(64), 0, s, (const uint32_t*)mark, (const uint32_t*)lop, cap,
@@ -1207,7 +1267,7 @@ static int step_staged(gr_engine* e, uint32_t nm, const gr_local_input* locals, 
     HIPCHK(hipGetLastError());
     if ((r = sort_keys(e, nm, positions, s))) return r;
     hipLaunchKernelGGL(io::encode_sorted, dim3(io_grid(nm)), blk, 0, s, dmsgs, (const uint32_t*)e->d_skeys.p,
-                       (const uint32_t*)e->d_sidx.p, nm, vin);
+                       (const uint32_t*)e->d_sidx.p, nm, vin, (uint32_t)e->config_entries);
     HIPCHK(hipGetLastError());
   }
   // ---- locals -> lane rows
@@ -1317,9 +1377,9 @@ int gr_bind_nodes(gr_engine* e, const uint64_t* cluster_ids, const uint64_t* nod
 extern "C++" template <int S>
 static void launch_route_wire(const grw_message* wm, uint32_t n, const grw_entry* we, uint64_t n_ents,
                               const io::NodeKey* nodes, uint32_t tcap, StateBase st, gr_message* out,
-                              uint32_t* flag, uint8_t* why, hipStream_t s) {
+                              uint32_t* flag, uint8_t* why, uint32_t ce, hipStream_t s) {
   hipLaunchKernelGGL((io::route_wire<S>), dim3(io_grid(n)), dim3(io::kIoBlock), 0, s, wm, n, we, n_ents, nodes, tcap,
-                     st, out, flag, why);
+                     st, out, flag, why, ce);
 }
 
 // The wire path's routing half (gr_step_wire, gr_step_wire_compact): decoded
@@ -1353,14 +1413,14 @@ static int wire_route(gr_engine* e, const struct grw_message* d_msgs, size_t n_m
     uint32_t* scal = (uint32_t*)e->d_scal.p;
     switch (e->S) {
       case 1: launch_route_wire<1>(d_msgs, nw, d_ents, n_ents, (const io::NodeKey*)e->d_nodes.p, e->nodes_cap, e->st,
-                                   (gr_message*)e->d_wrec.p, flag, (uint8_t*)e->d_why.p, s); break;
+                                   (gr_message*)e->d_wrec.p, flag, (uint8_t*)e->d_why.p, e->config_entries, s); break;
       case 3: launch_route_wire<3>(d_msgs, nw, d_ents, n_ents, (const io::NodeKey*)e->d_nodes.p, e->nodes_cap, e->st,
-                                   (gr_message*)e->d_wrec.p, flag, (uint8_t*)e->d_why.p, s); break;
+                                   (gr_message*)e->d_wrec.p, flag, (uint8_t*)e->d_why.p, e->config_entries, s); break;
       case 5: launch_route_wire<5>(d_msgs, nw, d_ents, n_ents, (const io::NodeKey*)e->d_nodes.p, e->nodes_cap, e->st,
-                                   (gr_message*)e->d_wrec.p, flag, (uint8_t*)e->d_why.p, s); break;
+                                   (gr_message*)e->d_wrec.p, flag, (uint8_t*)e->d_why.p, e->config_entries, s); break;
       default: launch_route_wire<GR_SMAX>(d_msgs, nw, d_ents, n_ents, (const io::NodeKey*)e->d_nodes.p,
                                           e->nodes_cap, e->st, (gr_message*)e->d_wrec.p, flag,
-                                          (uint8_t*)e->d_why.p, s); break;
+                                          (uint8_t*)e->d_why.p, e->config_entries, s); break;
     }
     HIPCHK(hipGetLastError());
     if ((r = io_scan(e, flag, pos, nw, s))) return r;
@@ -1542,7 +1602,8 @@ int gr_step_compact_begin(gr_engine* e, const gr_cinbox* in) {
     hipLaunchKernelGGL(io::check_raw_ticks_c, dim3(io_grid(nlc + nlx)), blk, 0, s, ci.loc, nlc, ci.lext, nlx, scal + 1);
     HIPCHK(hipGetLastError());
   }
-  hipLaunchKernelGGL(io::mark_inputs_c, dim3(io_grid(nm + nlc)), blk, 0, s, ci, S, cap, mark, scal + 1);
+  hipLaunchKernelGGL(io::mark_inputs_c, dim3(io_grid(nm + nlc)), blk, 0, s, ci, S, cap, mark, scal + 1,
+                     (uint32_t)e->config_entries);
   HIPCHK(hipGetLastError());
   if ((r = io_scan(e, mark, lop, cap, s))) return r;
   hipLaunchKernelGGL(io::finish_lanes, dim3(1), dim3(64), 0, s, (const uint32_t*)mark, (const uint32_t*)lop, cap,
@@ -1616,7 +1677,7 @@ int gr_step_compact_end(gr_engine* e, gr_coutbox* out) {
     HIPCHK(hipGetLastError());
     if ((r = sort_keys(e, nm, positions, s))) return r;
     hipLaunchKernelGGL(io::encode_sorted_c, dim3(io_grid(nm)), blk, 0, s, ci, (const uint32_t*)e->d_skeys.p,
-                       (const uint32_t*)e->d_sidx.p, vin);
+                       (const uint32_t*)e->d_sidx.p, vin, (uint32_t)e->config_entries);
     HIPCHK(hipGetLastError());
   }
   // ---- locals -> lane rows
@@ -2069,6 +2130,16 @@ int gr_set_snapshots(gr_engine* e, int on) {
 
 int gr_get_snapshots(const gr_engine* e) { return e ? (int)e->snapshots : GR_EINVAL; }
 
+int gr_set_config_entries(gr_engine* e, int on) {
+  if (!e) return GR_EINVAL;
+  std::lock_guard<std::mutex> guard(e->mu);
+  GR_REFUSE_PENDING(e);
+  e->config_entries = on ? 1 : 0;
+  return GR_OK;
+}
+
+int gr_get_config_entries(const gr_engine* e) { return e ? (int)e->config_entries : GR_EINVAL; }
+
 int gr_set_quiesce(gr_engine* e, int on) {
   if (!e) return GR_EINVAL;
   std::lock_guard<std::mutex> guard(e->mu);
@@ -2279,6 +2350,22 @@ int gr_coverage_snap_read(uint64_t* out, uint32_t n) {
 const char* gr_coverage_snap_names() {
 #define GR_COVER_NAME(x) #x ","
   return GR_COVER_SNAP_IDS(GR_COVER_NAME);
+#undef GR_COVER_NAME
+}
+// The config-change-entry handlers' table (gr_cover.h GR_COVER_CC_IDS), read the same way.
+int gr_coverage_cc_read(uint64_t* out, uint32_t n) {
+  if (!out || n < CC_N) return GR_EINVAL;
+  HIPCHK(hipDeviceSynchronize());
+  for (uint32_t k = 0; k < CC_N; ++k) out[k] = 0;
+  HIPCHK(cover_cc_read<1>(out));
+  HIPCHK(cover_cc_read<3>(out));
+  HIPCHK(cover_cc_read<5>(out));
+  HIPCHK(cover_cc_read<8>(out));
+  return (int)CC_N;
+}
+const char* gr_coverage_cc_names() {
+#define GR_COVER_NAME(x) #x ","
+  return GR_COVER_CC_IDS(GR_COVER_NAME);
 #undef GR_COVER_NAME
 }
 #endif

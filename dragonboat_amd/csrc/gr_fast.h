@@ -256,6 +256,14 @@ struct FastLane {
       // nx <= rsn covers entries in an older run and nx <= firstIndex-1
       // (InstallSnapshot path): with H_GE_LO, nx > rsn implies nx > firstIndex-1
       GF_BAIL(nruns == 0 || below_newest(nx - 1));  // nx <= rsn
+      // config entries on and pendingConfigChange set: entries at or below
+      // lastIndex as loaded may hold the config change, whose Replicate needs its
+      // marks (gpuraft.h); the general lane writes them from the group's record
+      if ((GR_CONFIG_ENTRIES_FORCE || kp.config_entries) && nx <= hi0 &&
+          (h_flags(hdr) & GR_F_PENDING_CONFIG_CHANGE)) {
+        GR_COVER_C(LEAN_HANDOVER);
+        GF_BAIL(true);
+      }
       const uint64_t cnt = hi - nx + 1;  // entries nx..hi, all in the newest run
       // limitSize (entryutils.go:50-63) keeps all iff their sum fits (Lane::send_replicate)
       // (cnt > max / eub as cnt * eub > max: exact while both are below 2^32; a

@@ -167,8 +167,15 @@ __host__ __device__ inline void set_u8_row(gr_peer& g, uint32_t row, uint32_t, u
   else g.read_index[row - GR_Q].ack_bits = v;
 }
 
-__host__ __device__ inline int validate_msg(const gr_message& m, uint32_t S, uint32_t cap) {
+// ce: config entries are on (gpuraft.h gr_set_config_entries): a Replicate with
+// reject set carries config-change marks, which must name entries of the message.
+__host__ __device__ inline int validate_msg(const gr_message& m, uint32_t S, uint32_t cap,
+                                            bool ce = GR_CONFIG_ENTRIES_FORCE) {
   if (m.peer >= cap || m.slot >= S) return GR_EINVAL;
+  if (ce && m.type == GR_REPLICATE && m.reject) {
+    if (m.hint <= m.log_index || m.hint - m.log_index > m.n_entries) return GR_EINVAL;
+    if (m.hint_high && (m.hint_high <= m.log_index || m.hint_high >= m.hint)) return GR_EINVAL;
+  }
   if (m.type > GR_TIMEOUT_NOW) return GR_EINVAL;
   if (m.n_runs > 2) return GR_EINVAL;
   if (m.n_entries == 0 && m.n_runs != 0) return GR_EINVAL;
@@ -206,10 +213,11 @@ __host__ __device__ inline void encode_msg(const Mailbox& mb, uint32_t k, const 
 // 1 | 2 for a ReplicateResp accept | 4 for a Replicate carrying its one entry.
 // A uniform Replicate is compact (LogTerm = Term, at most one entry at Term,
 // narrow Commit), so its compact decode equals the full one.
-__host__ __device__ inline uint32_t uniform_class(const gr_message& m) {
+// ce (config entries on): a marked Replicate travels as a full record.
+__host__ __device__ inline uint32_t uniform_class(const gr_message& m, bool ce = GR_CONFIG_ENTRIES_FORCE) {
   if (wide_term(m.term, m.log_term, m.run_term[0], m.run_term[1])) return 0;
   if (m.type == GR_REPLICATE_RESP) return m.reject ? 0u : 3u;  // an accept carries Term and LogIndex
-  if (m.type != GR_REPLICATE) return 0;
+  if (m.type != GR_REPLICATE || (ce && m.reject)) return 0;
   uint32_t cd;
   if (!commit_delta(m.commit, m.log_index, &cd) || m.log_term != m.term) return 0;
   if (m.n_entries == 0) return m.n_runs == 0 ? 1u : 0u;
@@ -218,13 +226,14 @@ __host__ __device__ inline uint32_t uniform_class(const gr_message& m) {
 // The count byte of a mailbox whose `count` messages (at(q), q < count) are
 // encoded: MB_UNIFORM with the term word written when they all allow it.
 template <class MsgAt>
-__host__ __device__ inline uint8_t count_byte(const Mailbox& mb, uint32_t count, MsgAt at) {
+__host__ __device__ inline uint8_t count_byte(const Mailbox& mb, uint32_t count, MsgAt at,
+                                              bool ce = GR_CONFIG_ENTRIES_FORCE) {
   if (count == 0 || count > kUniformMax) return (uint8_t)count;
   uint32_t cb = count | MB_UNIFORM;
   uint64_t t0 = 0;
   for (uint32_t q = 0; q < count; ++q) {
     const gr_message m = at(q);
-    const uint32_t u = uniform_class(m);
+    const uint32_t u = uniform_class(m, ce);
     if (!u) return (uint8_t)count;
     if (q == 0) {
       t0 = m.term;
@@ -266,6 +275,10 @@ __host__ __device__ inline gr_message decode_msg(const Mailbox& mb, uint32_t k) 
       if (m.n_runs == 2) {
         m.run2_offset = mb.run2(k);
         m.run_term[1] = (uint64_t)mb.t32(k, MT_RT1);
+      }
+      if (m.reject) {  // config-change marks (gpuraft.h): the device sets the bit only with config entries on
+        m.hint = mb.u64(k, MF_HINT);
+        m.hint_high = mb.u64(k, MF_HINT_HIGH);
       }
       break;
     case GR_REPLICATE_RESP:  // the device writes Hint only on a reject
@@ -540,13 +553,18 @@ __host__ __device__ inline bool pair_of(const gr_cmsg& a, const gr_cmsg& b, gr_c
   return true;
 }
 __host__ __device__ inline int validate_cmsg(const gr_cmsg& c, const gr_message* ext, uint32_t n_ext, uint32_t S,
-                                             uint32_t cap) {
+                                             uint32_t cap, bool ce = GR_CONFIG_ENTRIES_FORCE) {
   if (c.peer >= cap || c.slot >= S || c.type > GR_TIMEOUT_NOW) return GR_EINVAL;
   if (c.flags & GR_CM_EXT) {
     if (c.aux >= n_ext) return GR_EINVAL;
     const gr_message& m = ext[c.aux];
     if (m.peer != c.peer || m.slot != c.slot || m.type != c.type) return GR_EINVAL;
-    return validate_msg(m, S, cap);
+    return validate_msg(m, S, cap, ce);
+  }
+  if (ce && c.type == GR_REPLICATE && (c.flags & GR_CM_REJECT)) {  // marks in compact form: one entry, its index
+    const gr_message m = msg_of(c);
+    if (c.flags & GR_CM_PAIR) return GR_EINVAL;
+    if (validate_msg(m, S, cap, ce) != GR_OK) return GR_EINVAL;
   }
   if ((c.flags & GR_CM_ENTRY2) && !(c.flags & GR_CM_PAIR)) return GR_EINVAL;
   if ((c.flags & GR_CM_PAIR) && !(c.type == GR_REPLICATE ||

@@ -39,12 +39,13 @@ __device__ inline uint32_t io_tid() { return blockIdx.x * kIoBlock + threadIdx.x
 __device__ inline uint32_t io_stride() { return gridDim.x * kIoBlock; }
 
 // Validate every record (gr_host.h validate_msg) and flag the peers with input.
+// ce: config entries are on (a Replicate's reject bit means config-change marks).
 __global__ void mark_inputs(const gr_message* msgs, uint32_t n_msgs, const gr_local_input* loc, uint32_t n_loc,
-                            uint32_t S, uint32_t cap, uint32_t* mark, uint32_t* err) {
+                            uint32_t S, uint32_t cap, uint32_t* mark, uint32_t* err, uint32_t ce) {
   for (uint32_t k = io_tid(); k < n_msgs + n_loc; k += io_stride()) {
     if (k < n_msgs) {
       const gr_message& m = msgs[k];
-      if (host::validate_msg(m, S, cap) != GR_OK) {
+      if (host::validate_msg(m, S, cap, ce != 0) != GR_OK) {
         atomicOr(err, 1u);
         continue;
       }
@@ -136,7 +137,7 @@ __global__ void key_order(const uint32_t* cnt, const uint32_t* base, uint32_t nk
 // writes the count byte (GR_C + 1 = overflowed; the receiver escalates CAPACITY
 // at the first message that did not travel).
 __global__ void encode_sorted(const gr_message* msgs, const uint32_t* skeys, const uint32_t* sidx, uint32_t n,
-                              SpaceView v) {
+                              SpaceView v, uint32_t ce) {
   for (uint32_t s = io_tid(); s < n; s += io_stride()) {
     const uint32_t key = skeys[s];
     uint32_t r = 0;
@@ -144,8 +145,9 @@ __global__ void encode_sorted(const gr_message* msgs, const uint32_t* skeys, con
     const Mailbox mb = v.at(key);
     if (r < (uint32_t)GR_C) host::encode_msg(mb, r, msgs[sidx[s]]);
     if (s + 1 == n || skeys[s + 1] != key)  // the mailbox's last record: its count byte (uniform when it can be)
-      mb.cnt() = r < (uint32_t)GR_C ? host::count_byte(mb, r + 1, [&](uint32_t q) { return msgs[sidx[s - r + q]]; })
-                                    : (uint8_t)(GR_C + 1);
+      mb.cnt() = r < (uint32_t)GR_C
+                     ? host::count_byte(mb, r + 1, [&](uint32_t q) { return msgs[sidx[s - r + q]]; }, ce != 0)
+                     : (uint8_t)(GR_C + 1);
   }
 }
 
@@ -271,11 +273,11 @@ struct CInbox {
   uint32_t n_msgs, n_ext, n_loc, n_lext;
 };
 
-__global__ void mark_inputs_c(CInbox in, uint32_t S, uint32_t cap, uint32_t* mark, uint32_t* err) {
+__global__ void mark_inputs_c(CInbox in, uint32_t S, uint32_t cap, uint32_t* mark, uint32_t* err, uint32_t ce) {
   for (uint32_t k = io_tid(); k < in.n_msgs + in.n_loc; k += io_stride()) {
     if (k < in.n_msgs) {
       const gr_cmsg c = in.msgs[k];
-      if (host::validate_cmsg(c, in.ext, in.n_ext, S, cap) != GR_OK) {
+      if (host::validate_cmsg(c, in.ext, in.n_ext, S, cap, ce != 0) != GR_OK) {
         atomicOr(err, 1u);
         continue;
       }
@@ -302,7 +304,7 @@ __global__ void msg_keys_c(const gr_cmsg* msgs, uint32_t n, const uint32_t* lane
 // encode_sorted over compact records (expanded in registers). A GR_CM_PAIR
 // record is two messages: a record's first message lands after the messages of
 // the mailbox's earlier records.
-__global__ void encode_sorted_c(CInbox in, const uint32_t* skeys, const uint32_t* sidx, SpaceView v) {
+__global__ void encode_sorted_c(CInbox in, const uint32_t* skeys, const uint32_t* sidx, SpaceView v, uint32_t ce) {
   const uint32_t n = in.n_msgs;
   for (uint32_t s = io_tid(); s < n; s += io_stride()) {
     const uint32_t key = skeys[s];
@@ -326,7 +328,7 @@ __global__ void encode_sorted_c(CInbox in, const uint32_t* skeys, const uint32_t
           q -= k;
           ++x;
         }
-      }) : (uint8_t)(GR_C + 1);
+      }, ce != 0) : (uint8_t)(GR_C + 1);
   }
 }
 
@@ -470,7 +472,7 @@ enum : uint8_t {
 template <int S>
 __global__ void route_wire(const grw_message* wm, uint32_t n, const grw_entry* we, uint64_t n_ents,
                            const NodeKey* nodes, uint32_t tcap, StateBase st, gr_message* out, uint32_t* flag,
-                           uint8_t* why) {
+                           uint8_t* why, uint32_t ce) {
   using Rw = Rows<S>;
   for (uint32_t i = io_tid(); i < n; i += io_stride()) {
     const grw_message m = wm[i];
@@ -506,10 +508,15 @@ __global__ void route_wire(const grw_message* wm, uint32_t n, const grw_entry* w
       uint32_t runs = 0, run2 = 0;
       uint64_t rt0 = 0, rt1 = 0;
       bool cc = false, seq = true;
+      uint64_t cc1 = 0, cc2 = 0;  // the two highest indexes of config-change entries (entries ascend)
       if ((uint64_t)m.first_entry + m.n_entries > n_ents) w = WR_RUNS;
       for (uint32_t k = 0; w == WR_ROUTED && k < m.n_entries; ++k) {
         const grw_entry en = we[m.first_entry + k];
         cc = cc || en.type == 1;  // raftpb.ConfigChangeEntry
+        if (en.type == 1) {
+          cc2 = cc1;
+          cc1 = en.index;
+        }
         seq = seq && en.index == m.log_index + 1 + k;
         if (k == 0) {
           rt0 = en.term;
@@ -537,6 +544,11 @@ __global__ void route_wire(const grw_message* wm, uint32_t n, const grw_entry* w
       r.commit = m.commit;
       r.hint = m.hint;
       r.hint_high = m.hint_high;
+      if (ce && m.type == GR_REPLICATE) {  // the marks of gpuraft.h's convention, from the entries' types
+        r.reject = cc1 ? 1 : 0;
+        r.hint = cc1;
+        r.hint_high = cc2;
+      }
       r.run_term[0] = rt0;
       r.run_term[1] = rt1;
     }
@@ -1444,6 +1456,15 @@ __global__ void set_snapshot_recs(gr_snapshot_rec* recs, const uint32_t* slots, 
   for (uint32_t x = io_tid(); x < n; x += io_stride()) recs[slots[x]] = in[x];
 }
 __global__ void get_snapshot_recs(const gr_snapshot_rec* recs, const uint32_t* slots, gr_snapshot_rec* out, uint32_t n) {
+  for (uint32_t x = io_tid(); x < n; x += io_stride()) out[x] = recs[slots[x]];
+}
+
+// gr_set_cc_indexes / gr_get_cc_indexes: the side array of config-change index
+// records over a slot list (slots checked on the host: in range, each once).
+__global__ void set_cc_indexes(gr_cc_index* recs, const uint32_t* slots, const gr_cc_index* in, uint32_t n) {
+  for (uint32_t x = io_tid(); x < n; x += io_stride()) recs[slots[x]] = in[x];
+}
+__global__ void get_cc_indexes(const gr_cc_index* recs, const uint32_t* slots, gr_cc_index* out, uint32_t n) {
   for (uint32_t x = io_tid(); x < n; x += io_stride()) out[x] = recs[slots[x]];
 }
 

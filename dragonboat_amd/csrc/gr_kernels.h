@@ -1187,6 +1187,14 @@ hipError_t cover_snap_read(uint64_t* out) {
     for (uint32_t k = 0; k < CS_N; ++k) out[k] += h[k];
   return e;
 }
+template <int S>
+hipError_t cover_cc_read(uint64_t* out) {
+  unsigned long long h[CC_N];
+  const hipError_t e = hipMemcpyFromSymbol(h, HIP_SYMBOL(gr_cover_cc_dev), sizeof(h), 0, hipMemcpyDeviceToHost);
+  if (e == hipSuccess)
+    for (uint32_t k = 0; k < CC_N; ++k) out[k] += h[k];
+  return e;
+}
 #endif
 
 }  // namespace gr
@@ -1203,7 +1211,8 @@ hipError_t cover_snap_read(uint64_t* out) {
   template hipError_t cover_read<SS>(uint64_t*); \
   template hipError_t cover_elect_read<SS>(uint64_t*); \
   template hipError_t cover_quiesce_read<SS>(uint64_t*); \
-  template hipError_t cover_snap_read<SS>(uint64_t*);
+  template hipError_t cover_snap_read<SS>(uint64_t*);   \
+  template hipError_t cover_cc_read<SS>(uint64_t*);
 #else
 #define GR_INSTANTIATE_COVER(SS)
 #endif

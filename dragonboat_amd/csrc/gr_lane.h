@@ -12,7 +12,9 @@
 // the device or entirely by the host (one source of truth).
 // Elections (campaign, votes, promotion: the "elections" section below) run
 // here only with StepParams::elections set; off, they escalate. So do snapshots
-// (send and restore: the "snapshots" section) with StepParams::snapshots.
+// (send and restore: the "snapshots" section) with StepParams::snapshots, and
+// config-change proposals and promotions over uncommitted entries (the
+// "config-change entries" section) with StepParams::config_entries.
 //
 // Function-level citations are to /root/reference/internal/raft/*.go.
 #pragma once
@@ -143,6 +145,9 @@ struct Lane {
   // registers; after the run that stands they become gr_restored records, as the
   // promotion does, and the last one the group's snapshot record.
   uint32_t nrest = 0;
+  // config-change entries: this run has copied the group's gr_cc_index record to
+  // its staging record (StepParams::cc_stage) and works there
+  bool cc_live = false;
 
   // The general kernel's message prefetch (round 5, device builds, S <= 3): the
   // first kPfK messages of every in-mailbox, loaded before the message loop by
@@ -643,6 +648,10 @@ struct Lane {
             mb.t32(c, MT_RT1) = (uint32_t)(m.rt1);
           }
         }
+        if (m.flags & MFL_REJECT) {  // config-change marks (gpuraft.h): only cc_mark sets the bit
+          mb.u64(c, MF_HINT) = m.hint;
+          mb.u64(c, MF_HINT_HIGH) = m.hint_high;
+        }
         break;
       }
       case GR_REPLICATE_RESP:  // Hint is only read on a reject (decreaseTo, raft.go:1219)
@@ -678,7 +687,7 @@ struct Lane {
     const bool resp = m.type == GR_REPLICATE_RESP;
     const bool uni = resp ? !(m.flags & MFL_REJECT)
                           : m.type == GR_REPLICATE && commit_delta(m.commit, m.log_index, &cd0) &&
-                                m.log_term == mterm &&
+                                m.log_term == mterm && !(m.flags & MFL_REJECT) &&
                                 (m.n == 0 ? runs == 0 : (m.n == 1 && runs == 1 && m.rt0 == mterm));
     const uint32_t sh = 5 * j;
     if (c == 0) {
@@ -866,6 +875,7 @@ struct Lane {
       else if (s == GR_RETRY) set_rstate(j, GR_WAIT);
       else return GR_ESC_PANIC;
       dirty |= D_REM;
+      if (config_entries()) cc_mark(nx, m);
     } else {
       GR_COVER(SEND_EMPTY);
     }
@@ -1013,6 +1023,122 @@ struct Lane {
       }
       list[at] = r;
     }
+  }
+
+  // ---------------------------------------------------------------- config-change entries
+  // Everything here runs only with config entries on (gr_set_config_entries):
+  // off, the callers escalate as they always did. The group's record (gpuraft.h
+  // gr_cc_index: the two highest config-change indexes above committed) is not
+  // kept in registers: the first handler of a run that needs it copies it to the
+  // peer's staging record and works there; step() copies the staging record
+  // back after the stores of the run that stands, so an escalated item leaves no
+  // trace. The lane keeps one bit (cc_live).
+  GR_HD bool config_entries() const { return GR_CONFIG_ENTRIES_FORCE || kp.config_entries; }
+  GR_HD gr_cc_index* cc_recs() const {
+#if GR_CONFIG_ENTRIES_FORCE && !defined(__HIP_DEVICE_COMPILE__)
+    if (!kp.cc_rec) return cc_host_hook.cc_rec;
+#endif
+    return kp.cc_rec;
+  }
+  GR_HD gr_cc_index* cc_stage_base() const {
+#if GR_CONFIG_ENTRIES_FORCE && !defined(__HIP_DEVICE_COMPILE__)
+    if (!kp.cc_stage) return cc_host_hook.cc_stage;
+#endif
+    return kp.cc_stage;
+  }
+  // The staging record, filled from the group's record on first touch in a run;
+  // nullptr when the engine has no arrays (the caller escalates).
+  GR_HD gr_cc_index* cc() {
+    gr_cc_index* st = cc_stage_base();
+    const gr_cc_index* rec = cc_recs();
+    if (!st || !rec) return nullptr;
+    if (!cc_live) {
+      st[p].last = rec[p].last;
+      st[p].prev = rec[p].prev;
+      cc_live = true;
+    }
+    return st + p;
+  }
+  // handleLeaderPropose's config-change branch (raft.go:1132-1141) for the one
+  // entry about to be appended at lastIndex + 1; the caller has found the flag clear.
+  GR_HD int cc_proposed() {
+    gr_cc_index* r = cc();
+    if (!r) return GR_ESC_CONFIG_CHANGE;
+    GR_COVER_C(PROPOSED);
+    r->prev = r->last > committed ? r->last : 0;
+    r->last = hi + 1;
+    flags |= (uint32_t)GR_F_PENDING_CONFIG_CHANGE;
+    dirty |= D_FLAGS;
+    return 0;
+  }
+  // The marks of a Replicate carrying entries [nx, lastIndex] (gpuraft.h): a
+  // leader holds a config-change entry above committed only while its flag is set.
+  GR_HD void cc_mark(uint64_t nx, OutMsg& m) {
+    if (!(flags & GR_F_PENDING_CONFIG_CHANGE)) return;
+    const gr_cc_index* r = cc();
+    if (!r) return;
+    const uint64_t l = r->last, q = r->prev;
+    if (l >= nx && l > committed) {
+      m.flags |= MFL_REJECT;
+      m.hint = l;
+      if (q >= nx && q > committed) {
+        GR_COVER_C(SEND_MARK_TWO);
+        m.hint_high = q;
+      } else {
+        GR_COVER_C(SEND_MARK);
+      }
+    } else {
+      GR_COVER_C(SEND_NO_MARK);
+    }
+  }
+  // A truncating append at conflict index ci: recorded indexes >= ci go. With two
+  // uncommitted config changes in the log the record cannot say what lies below
+  // the one that stays: the host re-runs the item and reloads exact indexes.
+  GR_HD int cc_truncate(uint64_t ci) {
+    gr_cc_index* r = cc();
+    if (!r) return 0;
+    if (r->last < ci) {
+      GR_COVER_C(TRUNCATE_KEEP);
+      return 0;
+    }
+    if (r->prev > committed) {
+      GR_COVER_C(TRUNCATE_TWO);
+      return GR_ESC_CONFIG_CHANGE;
+    }
+    GR_COVER_C(TRUNCATE_DROP);
+    r->last = 0;  // prev is stale or 0
+    r->prev = 0;
+    return 0;
+  }
+  // An accepted Replicate's marks a > b merged into the record: the two highest
+  // distinct values.
+  GR_HD void cc_merge(uint64_t a, uint64_t b) {
+    gr_cc_index* r = cc();
+    if (!r) return;
+    GR_COVER_C(MERGE);
+    const uint64_t l = r->last, q = r->prev;
+    const uint64_t top = umax(l, a);
+    uint64_t second = 0;
+    second = (l < top && l > second) ? l : second;
+    second = (a < top && a > second) ? a : second;
+    second = (q < top && q > second) ? q : second;
+    second = (b < top && b > second) ? b : second;
+    r->last = top;
+    r->prev = second;
+  }
+  // preLeaderPromotionHandleConfigChange (raft.go:722-731): the count over
+  // (committed, lastIndex], before reset() and the empty entry.
+  GR_HD int cc_pending_count(uint32_t* n) {
+    const gr_cc_index* r = cc();
+    if (!r) return GR_ESC_UNSUPPORTED;
+    *n = (r->last > committed ? 1u : 0u) + (r->prev > committed ? 1u : 0u);
+    return 0;
+  }
+  GR_HD void cc_commit_record() {  // after the stores of the run that stands
+    gr_cc_index* rec = cc_recs();
+    const gr_cc_index* st = cc_stage_base();
+    rec[p].last = st[p].last;
+    rec[p].prev = st[p].prev;
   }
 
   GR_HD int broadcast_replicate() {  // raft.go:534-546
@@ -1281,6 +1407,7 @@ struct Lane {
         if (ci > hi + 1) return GR_ESC_PANIC;      // merge would hit a hole
         const uint64_t tprev = (ci - 1 == m.log_index) ? m.log_term : msg_term_at(m, ci - 1);
         if (tprev > msg_term_at(m, ci)) return GR_ESC_PANIC;  // checkEntriesToAppend
+        if (ci <= hi && config_entries()) GR_TRY(cc_truncate(ci));
         if (ci <= hi) merge_truncate(ci);
         win_truncate(ci);
         const uint32_t nr = (m.flags >> MFL_RUNS_SHIFT) & 3u;
@@ -1303,6 +1430,9 @@ struct Lane {
         committed = c;
         dirty |= D_COMMITTED;
       }
+      // marks at or below the message's commit are ignored (gpuraft.h): committed is at least that now
+      if ((m.flags & MFL_REJECT) && config_entries() && m.hint > committed)
+        cc_merge(m.hint, m.hint_high > committed ? m.hint_high : 0);
       r.log_index = last_idx;
     } else {
       GR_COVER(REP_REJECT);
@@ -1399,12 +1529,17 @@ struct Lane {
   // becomeLeader (raft.go:689-702) with appendEntries (:643-654) of the empty
   // entry. The device log has no entry types, so getPendingConfigChangeCount
   // (:903-917), which scans (committed, lastIndex] for config changes, is known
-  // to be 0 only when that range is empty: any other promotion goes to the host.
+  // to be 0 when that range is empty; otherwise the group's gr_cc_index record
+  // gives it with config entries on, and the promotion goes to the host without.
   GR_HD int become_leader() {
     need(G_CORE | G_LEAD | G_WIN | G_REM);
+    uint32_t ncc = 0;
     if (committed < hi) {
-      GR_COVER_E(PROMOTE_UNCOMMITTED);
-      return GR_ESC_UNSUPPORTED;
+      if (!config_entries()) {
+        GR_COVER_E(PROMOTE_UNCOMMITTED);
+        return GR_ESC_UNSUPPORTED;
+      }
+      GR_TRY(cc_pending_count(&ncc));
     }
     if (state == GR_FOLLOWER || state == GR_OBSERVER) return GR_ESC_PANIC;
     if (self >= (uint32_t)S) return GR_ESC_UNSUPPORTED;  // no remote of its own to advance
@@ -1412,6 +1547,17 @@ struct Lane {
     dirty |= D_STATE;
     GR_TRY(reset(term));
     leader_id = node_id;
+    if (ncc > 1) {
+      GR_COVER_C(PROMOTE_PANIC);
+      return GR_ESC_PANIC;  // "multiple uncommitted config change entries"
+    }
+    if (ncc == 1) {  // setPendingConfigChange, raft.go:727-729
+      GR_COVER_C(PROMOTE_PENDING);
+      flags |= (uint32_t)GR_F_PENDING_CONFIG_CHANGE;
+      dirty |= D_FLAGS;
+    } else if (committed < hi) {
+      GR_COVER_C(PROMOTE_CLEAR);
+    }
     if (nruns > 0 && last_run_term() > term) return GR_ESC_PANIC;  // checkEntriesToAppend
     win_push(hi + 1, term);
     hi += 1;
@@ -1688,6 +1834,10 @@ struct Lane {
               m.rt1 = w1.z;
             }
           }
+          if (m.flags & MFL_REJECT) {  // config-change marks: read only with config entries on
+            m.hint = hint;
+            m.hint_high = hint_high;
+          }
           break;
         case GR_REPLICATE_RESP:
           m.log_index = li;
@@ -1927,8 +2077,17 @@ struct Lane {
   // host can attribute the entries (gr_peer_result.propose_first): a drop
   // (selfRemoved, leader transfer) or a config change goes to the host.
   GR_HD int leader_forwarded_propose(const InMsg& m) {
-    if (m.flags & MFL_REJECT) return GR_ESC_CONFIG_CHANGE;
+    const bool cc = (m.flags & MFL_REJECT) != 0;
+    if (cc && (!config_entries() || m.n != 1)) return GR_ESC_CONFIG_CHANGE;
     if (m.n == 0 || self_removed() || leader_transfering()) return GR_ESC_UNSUPPORTED;
+    if (cc) {
+      if (flags & GR_F_PENDING_CONFIG_CHANGE) {
+        GR_COVER_C(PROPOSE_PENDING);
+        return GR_ESC_CONFIG_CHANGE;  // the reference replaces the entry: the host owns the payload
+      }
+      GR_COVER_C(PROPOSE_FWD);
+      GR_TRY(cc_proposed());
+    }
     GR_TRY(append_proposal(m.n));
     fwd_n++;
     fwd_entries += m.n;
@@ -1942,7 +2101,15 @@ struct Lane {
     if (state == GR_LEADER) {
       if (self_removed()) { GR_COVER(PROP_DROP_SELF_REMOVED); prop_result = GR_PROP_DROPPED; return 0; }
       if (leader_transfering()) { GR_COVER(PROP_DROP_TRANSFER); prop_result = GR_PROP_DROPPED; return 0; }
-      if (has_cc) return GR_ESC_CONFIG_CHANGE;
+      if (has_cc) {
+        if (!config_entries() || n != 1) return GR_ESC_CONFIG_CHANGE;
+        if (flags & GR_F_PENDING_CONFIG_CHANGE) {
+          GR_COVER_C(PROPOSE_PENDING);
+          return GR_ESC_CONFIG_CHANGE;  // the reference replaces the entry: the host owns the payload
+        }
+        GR_COVER_C(PROPOSE_LOCAL);
+        GR_TRY(cc_proposed());
+      }
       GR_COVER(PROP_APPEND);
       GR_TRY(append_proposal(n));
       prop_result = GR_PROP_APPENDED;
@@ -1985,6 +2152,7 @@ struct Lane {
     promoted = false;
     transfer_target = false;
     nrest = 0;
+    cc_live = false;
   }
   // This pass's promotion, for gr_promotions: one record, one returning atomic.
   GR_HD void report_promotion() {
@@ -2162,6 +2330,7 @@ struct Lane {
     store();
     if (promoted) report_promotion();  // of the run that stands (a re-run prefix included)
     if (nrest) report_restores();
+    if (cc_live) cc_commit_record();
     tclk[2] = lane_clock(kp);
 #pragma unroll 1
     for (uint32_t j = 0; j < (uint32_t)S; ++j) {  // every routed mailbox is rewritten each pass

@@ -693,6 +693,15 @@ struct StepParams {
   gr_snapshot_rec* rest_stage;
   uint32_t* rest_hdr;
   gr_restored* rest;
+  // config-change entries on the device (gr_set_config_entries): wave-uniform,
+  // tested only on the rare paths that need the record (gr_lane.h
+  // Lane::config_entries). cc_rec: the groups' gr_cc_index records by engine
+  // slot; cc_stage: one staging record per engine slot, where the lane that
+  // steps the peer works on a copy until its pass stands (it alone reads and
+  // writes it).
+  uint8_t config_entries;
+  gr_cc_index* cc_rec;
+  gr_cc_index* cc_stage;
 };
 // -DGR_ELECTIONS_FORCE=1: elections on whatever StepParams::elections says (the
 // test-only host lane's second build, whose harness zeroes its StepParams).
@@ -716,6 +725,20 @@ struct SnapHostHook {
   uint32_t rest_cap;
 };
 inline SnapHostHook snap_host_hook = {nullptr, nullptr, nullptr, nullptr, 0};
+#endif
+// -DGR_CONFIG_ENTRIES_FORCE=1: the same for StepParams::config_entries, and for
+// the host-side encoders and validators of gr_host.h (their `ce` defaults). A
+// host build takes the side arrays from cc_host_hook, which its entry point
+// fills (tests/native/hostlane_cc.hip).
+#ifndef GR_CONFIG_ENTRIES_FORCE
+#define GR_CONFIG_ENTRIES_FORCE 0
+#endif
+#if GR_CONFIG_ENTRIES_FORCE && !defined(__HIP_DEVICE_COMPILE__)
+struct CcHostHook {
+  gr_cc_index* cc_rec;    // by engine slot
+  gr_cc_index* cc_stage;  // by engine slot
+};
+inline CcHostHook cc_host_hook = {nullptr, nullptr};
 #endif
 // A tick-list entry's staged inputs (round 5): the fields the steady kernel
 // loads for every lane of a wave that is not steady (coalesced: the wave's

@@ -138,6 +138,14 @@ def load_library(path=LIB_PATH):
         lib.gr_get_snapshot_recs.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t]
         lib.gr_restored_snapshots.argtypes = [c.c_void_p, c.c_void_p, c.c_size_t, c.POINTER(c.c_size_t)]
         lib.gr_restore_remotes.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p]
+    if hasattr(lib, "gr_coverage_cc_read"):
+        lib.gr_coverage_cc_read.argtypes = [c.c_void_p, c.c_uint32]
+        lib.gr_coverage_cc_names.restype = c.c_char_p
+    if hasattr(lib, "gr_set_config_entries"):  # (older builds loaded for A/B runs lack config entries)
+        lib.gr_set_config_entries.argtypes = [c.c_void_p, c.c_int]
+        lib.gr_get_config_entries.argtypes = [c.c_void_p]
+        lib.gr_set_cc_indexes.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t]
+        lib.gr_get_cc_indexes.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t]
     if hasattr(lib, "gr_set_quiesce"):  # (older builds loaded for A/B runs lack the quiesce manager)
         lib.gr_set_quiesce.argtypes = [c.c_void_p, c.c_int]
         lib.gr_get_quiesce.argtypes = [c.c_void_p]
@@ -165,8 +173,11 @@ class Engine:
     """One engine = one device's slab of group slots (engine slots 0..max_peers-1)."""
 
     def __init__(self, max_peers, slots=3, device=0, max_entry_size=abi.MAX_ENTRY_SIZE, lib_path=None,
-                 elections=False, quiesce=False, snapshots=False):
-        """snapshots: send and restore snapshots on the device (gr_set_snapshots);
+                 elections=False, quiesce=False, snapshots=False, config_entries=False):
+        """config_entries: config-change proposals, their Replicate marks and promotions
+        over uncommitted entries on the device (gr_set_config_entries); False leaves
+        the default, which GR_CONFIG_ENTRIES=1 turns on.
+        snapshots: send and restore snapshots on the device (gr_set_snapshots);
         False leaves the default, which GR_SNAPSHOTS=1 turns on.
         elections: run elections on the device (gr_set_elections); False leaves
         the engine's default, which GR_ELECTIONS=1 in the environment turns on.
@@ -188,6 +199,34 @@ class Engine:
             self.set_quiesce(True)
         if snapshots:
             self.set_snapshots(True)
+        if config_entries:
+            self.set_config_entries(True)
+
+    def set_config_entries(self, on):
+        """Config-change entries on the device (gpuraft.h gr_set_config_entries)."""
+        _check(self.lib.gr_set_config_entries(self._h, 1 if on else 0), "gr_set_config_entries")
+
+    def get_config_entries(self):
+        return bool(self.lib.gr_get_config_entries(self._h))
+
+    def set_cc_indexes(self, slots, recs):
+        """The groups' config-change index records (abi.CC_INDEX: the two highest
+        ConfigChangeEntry indexes above committed) for a list of engine slots
+        (gr_set_cc_indexes): call it with every load of a group while the switch is on."""
+        slots = np.ascontiguousarray(slots, np.uint32)
+        recs = np.ascontiguousarray(recs, abi.CC_INDEX)
+        assert len(slots) == len(recs)
+        _check(self.lib.gr_set_cc_indexes(self._h, slots.ctypes.data if len(slots) else None,
+                                          recs.ctypes.data if len(recs) else None, len(slots)),
+               "gr_set_cc_indexes")
+
+    def get_cc_indexes(self, slots):
+        slots = np.ascontiguousarray(slots, np.uint32)
+        out = np.zeros(len(slots), abi.CC_INDEX)
+        _check(self.lib.gr_get_cc_indexes(self._h, slots.ctypes.data if len(slots) else None,
+                                          out.ctypes.data if len(out) else None, len(slots)),
+               "gr_get_cc_indexes")
+        return out
 
     def set_snapshots(self, on):
         """InstallSnapshot sends and restores on the device (gpuraft.h gr_set_snapshots)."""

@@ -76,8 +76,9 @@ enum gr_escalation {
    * snapshots off (gr_set_snapshots; on, see there for what is left); with elections off
    * (gr_set_elections) also votes, TimeoutNow and every candidate handler; with
    * elections on, a RequestVoteResp that would promote a candidate whose log
-   * has uncommitted entries (committed < last_index), and a RequestVote from a
-   * slot that is not a member */
+   * has uncommitted entries (committed < last_index; with config entries on,
+   * gr_set_config_entries, that promotion runs on the device), and a RequestVote
+   * from a slot that is not a member */
   GR_ESC_UNSUPPORTED = 3,
   /* campaign() (raft.go:779-807): every campaign with elections off; with
    * elections on, only the single-voter campaign (becomeCandidate and
@@ -90,7 +91,9 @@ enum gr_escalation {
   GR_ESC_ENTRY_SIZE = 8,     /* settings.Soft.MaxEntrySize may bind (raft.go:513) */
   GR_ESC_MSG_RUNS = 9,       /* Replicate entries span more than 2 term runs */
   GR_ESC_NONMEMBER = 10,     /* target node id has no remote slot */
-  GR_ESC_CONFIG_CHANGE = 11, /* proposal carries a ConfigChangeEntry (raft.go:1134-1143) */
+  /* proposal carries a ConfigChangeEntry (raft.go:1134-1143); with config
+   * entries on (gr_set_config_entries) only what that section lists */
+  GR_ESC_CONFIG_CHANGE = 11,
   GR_ESC_WIDE_TERM = 12      /* a message term >= 2^32 (device mailboxes carry 32-bit terms) */
 };
 
@@ -492,7 +495,8 @@ int gr_step_compact(gr_engine* e, const gr_cinbox* in, gr_coutbox* out);
  * that engine that steps it or uses them (gr_step, gr_step_compact{,_begin},
  * gr_step_device, gr_load_* / gr_sync_*, gr_set_locals, gr_bind_routes,
  * gr_compact_log, gr_commit_update, gr_apply_config_change, gr_restore_remotes, gr_notify_applied,
- * gr_set_snapshot_recs, gr_get_snapshot_recs, gr_restored_snapshots, gr_collect_results,
+ * gr_set_snapshot_recs, gr_get_snapshot_recs, gr_restored_snapshots, gr_set_cc_indexes,
+ * gr_get_cc_indexes, gr_collect_results,
  * gr_space_cold_used) returns GR_ESTATE and changes nothing. */
 int gr_step_compact_begin(gr_engine* e, const gr_cinbox* in);
 int gr_step_compact_end(gr_engine* e, gr_coutbox* out);
@@ -778,6 +782,76 @@ typedef struct gr_membership {
   uint64_t rand;         /* as gr_config_change.rand */
 } gr_membership;
 int gr_restore_remotes(gr_engine* e, const uint32_t* slots, const gr_membership* ms, size_t n, int32_t* status);
+/*
+ * Config-change entries on the device (off by default; GR_CONFIG_ENTRIES=1 in
+ * the environment at gr_create turns them on). The device log is term runs
+ * without entry types. Off, a Propose that carries a ConfigChangeEntry escalates
+ * GR_ESC_CONFIG_CHANGE and, with elections on, a promotion over uncommitted
+ * entries escalates GR_ESC_UNSUPPORTED, as ever; every result, record, message
+ * and escalation is what it was without this section. On, the general lane knows
+ * the one thing the reference asks of the types: getPendingConfigChangeCount
+ * (raft.go:903-917) is only used as 0, 1 or more, and the two highest
+ * config-change indexes above committed answer that,
+ * count = (last > committed) + (prev > committed). The switch applies to passes
+ * launched after the call; a captured graph keeps the setting it was captured
+ * with. gr_get_config_entries: 0 or 1 (GR_EINVAL for a NULL engine).
+ *
+ * The record: one gr_cc_index per engine slot in an array of its own, zeroed at
+ * gr_create (beside it one staging record per slot for the pass in flight);
+ * gr_load_* and gr_sync_* of a group do not touch it, so the host sets it with
+ * every load of a group while the switch is on. `last` is the index of the
+ * highest ConfigChangeEntry in (committed, last_index], `prev` the second
+ * highest, 0 none. A stored index at or below committed is stale and means 0;
+ * the device does not clear stale values. Slot rules are gr_set_snapshot_recs':
+ * out of range or listed twice is GR_ERANGE before anything is written, a call
+ * while a gr_step_compact_begin is pending GR_ESTATE. Nothing but the items below
+ * moves the record (not a restore, gr_compact_log, gr_commit_update or
+ * gr_apply_config_change: committed only grows, staleness covers them), and it
+ * belongs to the run that stands: an item that escalates leaves no trace in it.
+ *
+ * Message convention (switch on only): a GR_REPLICATE with reject = 1 carries in
+ * hint the highest index of a config-change entry among its entries
+ * log_index+1 .. log_index+n_entries and in hint_high the second highest, or 0.
+ * Marks at or below the message's own commit may be omitted and receivers ignore
+ * them, so a leader marks only indexes above its committed. On the way in the
+ * host, or gr_step_wire from the entries' types, sets the marks. gr_step and
+ * gr_step_compact refuse with GR_EINVAL, before anything is written, a marked
+ * Replicate whose hint lies outside (log_index, log_index+n_entries] or whose
+ * hint_high is neither 0 nor inside (log_index, hint). A marked Replicate always
+ * travels as a full record (a cold record in mailboxes; an ext record in the
+ * compact formats unless the existing flags carry it exactly), and
+ * gr_space_decode returns its hint / hint_high.
+ *
+ * With the switch on:
+ *   Propose   a leader's local proposal with propose_has_config_change and
+ *     propose_entries == 1 (Peer.ProposeConfigChange sends exactly one entry),
+ *     or a forwarded Propose with the reject bit and n_entries == 1, while
+ *     GR_F_PENDING_CONFIG_CHANGE is clear: sets the flag, appends, records
+ *     prev = last (if above committed) and last = the new index, broadcasts
+ *     (handleLeaderPropose, raft.go:1125-1146). GR_PROP_APPENDED / n_forwarded as
+ *     for any proposal.
+ *   Send      every Replicate whose entries include a config-change index above
+ *     the sender's committed carries the marks.
+ *   Receive   an accepted Replicate merges its marks into the record; a
+ *     truncating append drops recorded indexes at or above the conflict index first.
+ *   Promote   becomeLeader (raft.go:689-702) over uncommitted entries: count 2 is
+ *     GR_ESC_PANIC ("multiple uncommitted config change entries"), count 1 sets
+ *     GR_F_PENDING_CONFIG_CHANGE after reset().
+ * What still escalates GR_ESC_CONFIG_CHANGE with the switch on: a config change
+ * proposed while one is pending (the reference replaces the entry by an empty
+ * one, and the host owns the payload), a config change in a batch of more than
+ * one entry, and a truncating Replicate on a log that held two uncommitted
+ * config changes (last at or above the conflict index and prev above committed:
+ * the record cannot say what lies below; the host re-runs the item and reloads
+ * the group with exact indexes).
+ */
+int gr_set_config_entries(gr_engine* e, int on);
+int gr_get_config_entries(const gr_engine* e);
+typedef struct gr_cc_index {
+  uint64_t last, prev;
+} gr_cc_index;
+int gr_set_cc_indexes(gr_engine* e, const uint32_t* slots, const gr_cc_index* recs, size_t n);
+int gr_get_cc_indexes(gr_engine* e, const uint32_t* slots, gr_cc_index* out, size_t n);
 /*
  * The quiesce manager on the device (off by default; GR_QUIESCE_ON_DEVICE=1 in
  * the environment at gr_create turns it on). In the reference every node owns a
