@@ -149,6 +149,25 @@ class WireUnrouted(ctypes.Structure):
 
 WIRE_REASONS = ["routed", "no_peer", "nonmember", "snapshot", "type", "runs", "index"]
 
+# Entry-free outbox mail by wire (gpuraft.h gr_step_wire_out)
+TARGET_HOST = 0xFFFFFFFF
+MAX_TARGETS = 256
+WIRE_OUT_CFG = np.dtype([("deployment_id", u64), ("source_off", u64), ("source_len", u32), ("bin_ver", u32),
+                         ("max_batch_msgs", u32), ("pad", u32)])
+assert WIRE_OUT_CFG.itemsize == 32
+
+
+class WireOutCfg(ctypes.Structure):
+    _fields_ = [("deployment_id", ctypes.c_uint64), ("source_off", ctypes.c_uint64),
+                ("source_len", ctypes.c_uint32), ("bin_ver", ctypes.c_uint32),
+                ("max_batch_msgs", ctypes.c_uint32), ("pad", ctypes.c_uint32)]
+
+
+class WireOut(ctypes.Structure):
+    _fields_ = [("d_batches", ctypes.c_void_p), ("n_batches", ctypes.c_size_t),
+                ("d_msgs", ctypes.c_void_p), ("n_msgs", ctypes.c_size_t),
+                ("batch_target", ctypes.c_void_p)]
+
 
 class CInbox(ctypes.Structure):
     _fields_ = [("msgs", ctypes.c_void_p), ("n_msgs", ctypes.c_size_t),
@@ -202,6 +221,7 @@ EXPORTS = [
     "gr_pack_messages", "gr_unpack_messages", "gr_cmsg_count", "gr_pair_messages", "gr_pack_locals",
     "gr_collect_results", "gr_space_decode", "gr_space_encode", "gr_timing_begin", "gr_timing_end",
     "gr_bind_nodes", "gr_step_wire", "gr_step_wire_compact",
+    "gr_bind_targets", "gr_step_wire_out", "gr_step_compact_wire_out", "gr_wire_out_host",
     "gr_graph_capture", "gr_graph_replay", "gr_graph_destroy",
     "gr_set_elections", "gr_get_elections", "gr_promotions",
     "gr_set_snapshots", "gr_get_snapshots", "gr_set_snapshot_recs", "gr_get_snapshot_recs", "gr_restored_snapshots",

@@ -432,6 +432,27 @@ def _build_sanitized(force):
     return ORACLE_SAN_LIB, HOSTLANE_SAN_LIB
 
 
+WIRE_OUT_SAN_BIN = os.path.join(ROOT, "tests", "_build", "wire_out_san")
+
+
+def build_wire_out_san(force=False):
+    """tests/_build/wire_out_san: a stand-alone CPU program (its own main) that
+    drives gr_wire_out_host's code (gr_host.h) over seeded records under ASAN +
+    UBSAN, for tests/test_wire_out_host.py. Host code only; it is run directly."""
+    os.makedirs(os.path.dirname(WIRE_OUT_SAN_BIN), exist_ok=True)
+    src = os.path.join(ROOT, "tests", "native", "wire_out_san.hip")
+    deps = [src, os.path.join(ROOT, "include", "gpuraft.h"), os.path.join(ROOT, "include", "gpuraft_wire.h")] + \
+        [os.path.join(CSRC, f) for f in ("gr_host.h", "gr_layout.h", "gr_quiesce.h")]
+    if not (force or _stale(WIRE_OUT_SAN_BIN, deps)):
+        return WIRE_OUT_SAN_BIN
+    with _locked(WIRE_OUT_SAN_BIN):
+        if force or _stale(WIRE_OUT_SAN_BIN, deps):
+            _run([HIPCC, "--cuda-host-only", "-O1", "-g", "-std=c++17", "-fno-gpu-sanitize",
+                  *[a for f in SAN_FLAGS for a in ("-Xarch_host", f)],
+                  "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, src, "-o", WIRE_OUT_SAN_BIN])
+    return WIRE_OUT_SAN_BIN
+
+
 def build_wire(force=False):
     """libgrwire.so: the wire codec (include/gpuraft_wire.h)."""
     os.makedirs(os.path.dirname(WIRE_LIB), exist_ok=True)

@@ -168,6 +168,15 @@ struct gr_engine {
   Buf d_nodes;              // gr_bind_nodes: (cluster, node) -> slot table
   Buf d_wrec, d_why, d_unr; // gr_step_wire: routed records, per-message reason, unrouted indices
   uint32_t nodes_cap = 0;
+  // gr_step_wire_out: per-slot cluster ids (gr_bind_nodes), send queues per
+  // (slot, remote slot) (gr_bind_targets), and the pass's grouping scratch and
+  // records (gr_io.h wire_out_*)
+  Buf d_cluster, d_target;
+  uint32_t n_targets = 0;
+  Buf d_wf, d_wrank, d_wcnt, d_wbase, d_wplan, d_wtot, d_wmsgs, d_wbat, d_wbt;
+  uint8_t* h_wbt = nullptr;   // pinned: batch_target
+  uint8_t* h_wtot = nullptr;  // pinned: message and batch totals
+  size_t h_wbt_bytes = 0, h_wtot_bytes = 0;
   uint8_t* h_unr = nullptr;  // pinned: unrouted indices + reasons
   size_t h_unr_bytes = 0;
   uint8_t* h_inmsgs = nullptr;   // pinned inbox the caller may fill in place (gr_inbox_reserve)
@@ -579,10 +588,12 @@ void gr_destroy(gr_engine* e) {
                             &e->d_idx, &e->d_skeys, &e->d_sidx, &e->d_win, &e->d_oc, &e->d_off, &e->d_tmp,
                             &e->d_scal, &e->d_outmsgs, &e->d_results, &e->d_peers, &e->d_slots, &e->d_ext,
                             &e->d_lext, &e->d_oc64, &e->d_off64, &e->d_rx, &e->d_roff, &e->d_outext,
-                            &e->d_resext, &e->d_nodes, &e->d_wrec, &e->d_why, &e->d_unr, &e->d_kcnt, &e->d_kbase})
+                            &e->d_resext, &e->d_nodes, &e->d_wrec, &e->d_why, &e->d_unr, &e->d_kcnt, &e->d_kbase,
+                            &e->d_cluster, &e->d_target, &e->d_wf, &e->d_wrank, &e->d_wcnt, &e->d_wbase, &e->d_wplan,
+                            &e->d_wtot, &e->d_wmsgs, &e->d_wbat, &e->d_wbt})
     if (b->p) (void)hipFree(b->p);
   for (uint8_t* h : {e->h_outmsgs, e->h_results, e->h_scal, e->h_inmsgs, e->h_inlocals, e->h_inext, e->h_inlext,
-                     e->h_outext, e->h_resext, e->h_unr})
+                     e->h_outext, e->h_resext, e->h_unr, e->h_wbt, e->h_wtot})
     if (h) (void)hipHostFree(h);
   if (e->stream) (void)hipStreamDestroy(e->stream);
   delete e;
@@ -1198,12 +1209,14 @@ int gr_space_decode(const void* space_host, uint32_t n_chunks, uint32_t position
 // The device pass of gr_step over nm gr_message records already in e->d_msgs
 // (copied from the host by gr_step, or routed from decoded wire records by
 // gr_step_wire) and nlc host local inputs. Caller holds e->mu.
-static int pack_out_compact(gr_engine* e, uint32_t nl, const SpaceView& vout, gr_coutbox* out, PhaseClock* cl);
+static int pack_out_compact(gr_engine* e, uint32_t nl, const SpaceView& vout, gr_coutbox* out, PhaseClock* cl,
+                            const gr_wire_out_cfg* wcfg = nullptr, gr_wire_out* wout = nullptr);
 
 // gr_step's device pipeline from inbox records in HBM (e->d_msgs); the outbox as
 // full records (out) or, with cout, as compact records (gr_step_wire_compact)
 static int step_staged(gr_engine* e, uint32_t nm, const gr_local_input* locals, uint32_t nlc, gr_outbox* out,
-                       gr_coutbox* cout = nullptr) {
+                       gr_coutbox* cout = nullptr, const gr_wire_out_cfg* wcfg = nullptr,
+                       gr_wire_out* wout = nullptr) {
   if (out) {
     out->msgs = nullptr;
     out->n_msgs = 0;
@@ -1295,7 +1308,7 @@ static int step_staged(gr_engine* e, uint32_t nm, const gr_local_input* locals, 
   e->routes_bound = false;  // and RT_IDENTITY replaced the bound routes
   if (cout) {
     PhaseClock clk;
-    return pack_out_compact(e, nl, vout, cout, &clk);
+    return pack_out_compact(e, nl, vout, cout, &clk, wcfg, wout);
   }
   // ---- outbox mailboxes + lane results -> records
   if ((r = grow_device(&e->d_oc.p, &e->d_oc.n, (size_t)nl * 4))) return r;
@@ -1370,7 +1383,33 @@ int gr_bind_nodes(gr_engine* e, const uint64_t* cluster_ids, const uint64_t* nod
   int r;
   if ((r = grow_device(&e->d_nodes.p, &e->d_nodes.n, (size_t)tcap * sizeof(io::NodeKey)))) return r;
   HIPCHK(hipMemcpy(e->d_nodes.p, t.data(), (size_t)tcap * sizeof(io::NodeKey), hipMemcpyHostToDevice));
+  // the cluster id of every slot (0 above n): the outbound records' ClusterID
+  const size_t cap = e->cfg.max_peers;
+  if ((r = grow_device(&e->d_cluster.p, &e->d_cluster.n, cap * 8 + 8))) return r;
+  HIPCHK(hipMemset(e->d_cluster.p, 0, cap * 8));
+  if (n) HIPCHK(hipMemcpy(e->d_cluster.p, cluster_ids, (size_t)n * 8, hipMemcpyHostToDevice));
   e->nodes_cap = tcap;
+  return GR_OK;
+}
+
+// gr_bind_targets: the send queue of every (engine slot, remote slot) pair. The
+// caller's rows hold gr_config.slots values; the device copy has the instantiated
+// slot count's (e->S) columns per row, as the kernels index it, the columns the
+// configuration does not have filled with GR_TARGET_HOST.
+int gr_bind_targets(gr_engine* e, const uint32_t* target_of, uint32_t n_peers, uint32_t n_targets) {
+  if (!e || n_peers > e->cfg.max_peers) return GR_EINVAL;
+  const uint32_t slots = e->cfg.slots, S = e->S;
+  if (!host::wire_out_args_ok(target_of, (size_t)n_peers * slots, n_targets, nullptr)) return GR_EINVAL;
+  std::lock_guard<std::mutex> guard(e->mu);
+  GR_REFUSE_PENDING(e);
+  const size_t all = (size_t)e->cfg.max_peers * S;
+  std::vector<uint32_t> t(all, GR_TARGET_HOST);
+  for (uint32_t p = 0; p < n_peers; ++p)
+    std::copy(target_of + (size_t)p * slots, target_of + (size_t)(p + 1) * slots, t.begin() + (size_t)p * S);
+  int r;
+  if ((r = grow_device(&e->d_target.p, &e->d_target.n, all * 4 + 4))) return r;
+  HIPCHK(hipMemcpy(e->d_target.p, t.data(), all * 4, hipMemcpyHostToDevice));
+  e->n_targets = n_targets;
   return GR_OK;
 }
 
@@ -1476,10 +1515,43 @@ int gr_step_wire_compact(gr_engine* e, const struct grw_message* d_msgs, size_t 
   return step_staged(e, nm, locals, (uint32_t)n_locals, nullptr, out);
 }
 
+int gr_step_wire_out(gr_engine* e, const struct grw_message* d_msgs, size_t n_msgs, const struct grw_entry* d_ents,
+                     size_t n_ents, const gr_local_input* locals, size_t n_locals, gr_coutbox* out,
+                     gr_wire_unrouted* unrouted, const gr_wire_out_cfg* cfg, gr_wire_out* wout) {
+  if (!e || !out || !unrouted || !cfg || !wout || (n_msgs && !d_msgs) || (n_locals && !locals)) return GR_EINVAL;
+  if (n_msgs + n_locals >= 0x80000000ull || cfg->max_batch_msgs == 0) return GR_EINVAL;
+  std::lock_guard<std::mutex> guard(e->mu);
+  GR_REFUSE_PENDING(e);
+  if (!e->nodes_cap || !e->n_targets) return GR_ESTATE;  // gr_bind_nodes and gr_bind_targets first
+  memset(wout, 0, sizeof(*wout));
+  uint32_t nm;
+  int r;
+  if ((r = wire_route(e, d_msgs, n_msgs, d_ents, n_ents, unrouted, &nm))) return r;
+  return step_staged(e, nm, locals, (uint32_t)n_locals, nullptr, out, cfg, wout);
+}
+
+extern "C++" template <int S>
+static void launch_wire_out_group(const SpaceView& vout, uint32_t nl, uint32_t nblk, const uint32_t* pol,
+                                  const uint32_t* target_of, uint32_t T, uint8_t* wf, uint32_t* rank, uint32_t* cnt,
+                                  hipStream_t s) {
+  hipLaunchKernelGGL((io::wire_out_group<S>), dim3(nblk), dim3(io::kIoBlock), 0, s, vout, nl, pol, target_of, T, wf,
+                     rank, cnt);
+}
+extern "C++" template <int S>
+static void launch_wire_out_scatter(const SpaceView& vout, uint32_t nl, uint32_t nblk, const uint32_t* pol,
+                                    const uint32_t* target_of, StateBase st, const uint64_t* cluster_of,
+                                    const uint8_t* wf, const uint32_t* rank, const uint32_t* base,
+                                    const uint32_t* plan, uint32_t T, uint32_t mbm, grw_message* wmsgs,
+                                    hipStream_t s) {
+  hipLaunchKernelGGL((io::wire_out_scatter<S>), dim3(nblk), dim3(io::kIoBlock), 0, s, vout, nl, pol, target_of, st,
+                     cluster_of, wf, rank, base, plan, T, mbm, wmsgs);
+}
+
 // The outbox mailboxes and lane results of the pass just launched, as compact
 // records (+ ext records where they do not fit), downloaded into engine-owned
 // pinned memory: gr_step_compact_end and gr_step_wire_compact.
-static int pack_out_compact(gr_engine* e, uint32_t nl, const SpaceView& vout, gr_coutbox* out, PhaseClock* cl) {
+static int pack_out_compact(gr_engine* e, uint32_t nl, const SpaceView& vout, gr_coutbox* out, PhaseClock* cl,
+                            const gr_wire_out_cfg* wcfg, gr_wire_out* wout) {
   PhaseClock& clk = *cl;
   const uint32_t S = e->S;
   const hipStream_t s = e->stream;
@@ -1497,7 +1569,37 @@ static int pack_out_compact(gr_engine* e, uint32_t nl, const SpaceView& vout, gr
   uint64_t* off = (uint64_t*)e->d_off64.p;
   uint32_t* rx = (uint32_t*)e->d_rx.p;
   uint32_t* roff = (uint32_t*)e->d_roff.p;
-  hipLaunchKernelGGL(io::out_counts_c, dim3(io_grid(nl)), blk, 0, s, vout, e->ln, e->st, nl, S, oc, rx);
+  // ---- gr_step_wire_out: the entry-free mailboxes leave as MessageBatch records
+  // (gr_io.h wire_out_*): classified and ranked first, so the compact pack skips them
+  const uint8_t* wf = nullptr;
+  const uint32_t T = e->n_targets, nblk = (nl + io::kIoBlock - 1) / io::kIoBlock;
+  if (wout) {
+    const size_t pairs = (size_t)nl * S, cells = (size_t)T * nblk;
+    if ((r = grow_device(&e->d_wf.p, &e->d_wf.n, pairs))) return r;
+    if ((r = grow_device(&e->d_wrank.p, &e->d_wrank.n, pairs * 4))) return r;
+    if ((r = grow_device(&e->d_wcnt.p, &e->d_wcnt.n, cells * 4))) return r;
+    if ((r = grow_device(&e->d_wbase.p, &e->d_wbase.n, cells * 4))) return r;
+    if ((r = grow_device(&e->d_wplan.p, &e->d_wplan.n, (2 * (size_t)GR_MAX_TARGETS + 2) * 4))) return r;
+    if ((r = grow_device(&e->d_wtot.p, &e->d_wtot.n, 8))) return r;
+    if ((r = grow_pinned(&e->h_wtot, &e->h_wtot_bytes, 8))) return r;
+    const uint32_t* tgt = (const uint32_t*)e->d_target.p;
+    uint32_t* wrank = (uint32_t*)e->d_wrank.p;
+    uint32_t* wcnt = (uint32_t*)e->d_wcnt.p;
+    switch (S) {
+      case 1: launch_wire_out_group<1>(vout, nl, nblk, peer_of_lane, tgt, T, (uint8_t*)e->d_wf.p, wrank, wcnt, s); break;
+      case 3: launch_wire_out_group<3>(vout, nl, nblk, peer_of_lane, tgt, T, (uint8_t*)e->d_wf.p, wrank, wcnt, s); break;
+      case 5: launch_wire_out_group<5>(vout, nl, nblk, peer_of_lane, tgt, T, (uint8_t*)e->d_wf.p, wrank, wcnt, s); break;
+      default: launch_wire_out_group<GR_SMAX>(vout, nl, nblk, peer_of_lane, tgt, T, (uint8_t*)e->d_wf.p, wrank, wcnt, s); break;
+    }
+    HIPCHK(hipGetLastError());
+    if ((r = io_scan(e, wcnt, (uint32_t*)e->d_wbase.p, (uint32_t)cells, s))) return r;
+    hipLaunchKernelGGL(io::wire_out_plan, dim3(1), blk, 0, s, (const uint32_t*)wcnt, (const uint32_t*)e->d_wbase.p, T,
+                       nblk, wcfg->max_batch_msgs, (uint32_t*)e->d_wplan.p, (uint32_t*)e->d_wtot.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(e->h_wtot, e->d_wtot.p, 8, hipMemcpyDeviceToHost, s));
+    wf = (const uint8_t*)e->d_wf.p;
+  }
+  hipLaunchKernelGGL(io::out_counts_c, dim3(io_grid(nl)), blk, 0, s, vout, e->ln, e->st, nl, S, oc, rx, wf);
   HIPCHK(hipGetLastError());
   if ((r = io_scan64(e, oc, off, nl, s))) return r;
   if ((r = io_scan(e, rx, roff, nl, s))) return r;
@@ -1524,10 +1626,39 @@ static int pack_out_compact(gr_engine* e, uint32_t nl, const SpaceView& vout, gr
   if (rext) HIPCHK(hipMemcpyAsync(e->h_resext, e->d_resext.p, rxbytes, hipMemcpyDeviceToHost, s));
   if (total) {
     hipLaunchKernelGGL(io::pack_outbox_c, dim3(io_grid(nl)), blk, 0, s, vout, nl, S, (const uint64_t*)off,
-                       (const uint32_t*)peer_of_lane, (gr_cmsg*)e->d_outmsgs.p, (gr_message*)e->d_outext.p);
+                       (const uint32_t*)peer_of_lane, (gr_cmsg*)e->d_outmsgs.p, (gr_message*)e->d_outext.p, wf);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(e->h_outmsgs, e->d_outmsgs.p, mbytes, hipMemcpyDeviceToHost, s));
     if (text) HIPCHK(hipMemcpyAsync(e->h_outext, e->d_outext.p, xbytes, hipMemcpyDeviceToHost, s));
+  }
+  uint32_t wn = 0, wnb = 0;
+  if (wout) {  // the totals came down with the counts above
+    wn = ((uint32_t*)e->h_wtot)[0];
+    wnb = ((uint32_t*)e->h_wtot)[1];
+    if ((r = grow_device(&e->d_wmsgs.p, &e->d_wmsgs.n, (size_t)wn * sizeof(grw_message) + 1))) return r;
+    if ((r = grow_device(&e->d_wbat.p, &e->d_wbat.n, (size_t)wnb * sizeof(grw_batch) + 1))) return r;
+    if ((r = grow_device(&e->d_wbt.p, &e->d_wbt.n, (size_t)wnb * 4 + 4))) return r;
+    if ((r = grow_pinned(&e->h_wbt, &e->h_wbt_bytes, (size_t)wnb * 4 + 4))) return r;
+    if (wn) {
+      const uint32_t* tgt = (const uint32_t*)e->d_target.p;
+      const uint64_t* clu = (const uint64_t*)e->d_cluster.p;
+      const uint32_t* wrank = (const uint32_t*)e->d_wrank.p;
+      const uint32_t* wbase = (const uint32_t*)e->d_wbase.p;
+      const uint32_t* plan = (const uint32_t*)e->d_wplan.p;
+      const uint32_t mbm = wcfg->max_batch_msgs;
+      grw_message* wm = (grw_message*)e->d_wmsgs.p;
+      switch (S) {
+        case 1: launch_wire_out_scatter<1>(vout, nl, nblk, peer_of_lane, tgt, e->st, clu, wf, wrank, wbase, plan, T, mbm, wm, s); break;
+        case 3: launch_wire_out_scatter<3>(vout, nl, nblk, peer_of_lane, tgt, e->st, clu, wf, wrank, wbase, plan, T, mbm, wm, s); break;
+        case 5: launch_wire_out_scatter<5>(vout, nl, nblk, peer_of_lane, tgt, e->st, clu, wf, wrank, wbase, plan, T, mbm, wm, s); break;
+        default: launch_wire_out_scatter<GR_SMAX>(vout, nl, nblk, peer_of_lane, tgt, e->st, clu, wf, wrank, wbase, plan, T, mbm, wm, s); break;
+      }
+      HIPCHK(hipGetLastError());
+      hipLaunchKernelGGL(io::wire_out_batches, dim3(io_grid(wnb)), blk, 0, s, plan, T, *wcfg, wnb,
+                         (grw_batch*)e->d_wbat.p, (uint32_t*)e->d_wbt.p);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipMemcpyAsync(e->h_wbt, e->d_wbt.p, (size_t)wnb * 4, hipMemcpyDeviceToHost, s));
+    }
   }
   HIPCHK(hipStreamSynchronize(s));
   clk.mark("pack+download");
@@ -1540,21 +1671,34 @@ static int pack_out_compact(gr_engine* e, uint32_t nl, const SpaceView& vout, gr
   out->n_results = nl;
   out->ext_results = rext ? (gr_peer_result*)e->h_resext : nullptr;
   out->n_ext_results = rext;
+  if (wout) {
+    wout->d_batches = wnb ? (grw_batch*)e->d_wbat.p : nullptr;
+    wout->n_batches = wnb;
+    wout->d_msgs = wn ? (const grw_message*)e->d_wmsgs.p : nullptr;
+    wout->n_msgs = wn;
+    wout->batch_target = wnb ? (const uint32_t*)e->h_wbt : nullptr;
+  }
   return GR_OK;
 }
 
 // gr_step with compact records (gpuraft.h gr_cmsg / gr_clocal / gr_cresult):
 // the same device passes; records expand in registers on the way in and are
 // packed (with ext records for what does not fit) on the way out.
+static int compact_begin_locked(gr_engine* e, const gr_cinbox* in);
 int gr_step_compact_begin(gr_engine* e, const gr_cinbox* in) {
   if (!e || !in) return GR_EINVAL;
+  std::lock_guard<std::mutex> guard(e->mu);
+  return compact_begin_locked(e, in);
+}
+
+// gr_step_compact_begin with e->mu held
+static int compact_begin_locked(gr_engine* e, const gr_cinbox* in) {
   if ((in->n_msgs && !in->msgs) || (in->n_locals && !in->locals) || (in->n_ext_msgs && !in->ext_msgs) ||
       (in->n_ext_locals && !in->ext_locals))
     return GR_EINVAL;
   if (in->n_msgs + in->n_locals >= 0x80000000ull || in->n_ext_msgs >= 0x80000000ull ||
       in->n_ext_locals >= 0x80000000ull)
     return GR_EINVAL;
-  std::lock_guard<std::mutex> guard(e->mu);
   if (e->cpend.on) return GR_EINVAL;  // the previous begin was not ended
   GR_REFUSE_PENDING(e);
   PhaseClock clk;  // GR_PHASES=1: per-phase host times on stderr
@@ -1624,9 +1768,15 @@ int gr_step_compact_begin(gr_engine* e, const gr_cinbox* in) {
   return GR_OK;
 }
 
+static int compact_end_locked(gr_engine* e, gr_coutbox* out, const gr_wire_out_cfg* wcfg, gr_wire_out* wout);
 int gr_step_compact_end(gr_engine* e, gr_coutbox* out) {
   if (!e || !out) return GR_EINVAL;
   std::lock_guard<std::mutex> guard(e->mu);
+  return compact_end_locked(e, out, nullptr, nullptr);
+}
+
+// gr_step_compact_end with e->mu held; with wout, gr_step_compact_wire_out's second half
+static int compact_end_locked(gr_engine* e, gr_coutbox* out, const gr_wire_out_cfg* wcfg, gr_wire_out* wout) {
   if (!e->cpend.on) return GR_EINVAL;  // no pass was begun
   const gr_engine::CPending pend = e->cpend;
   e->cpend.on = false;
@@ -1703,7 +1853,7 @@ int gr_step_compact_end(gr_engine* e, gr_coutbox* out) {
   e->passes++;
   e->locals_set = false;
   e->routes_bound = false;
-  if ((r = pack_out_compact(e, nl, vout, out, &clk))) return r;
+  if ((r = pack_out_compact(e, nl, vout, out, &clk, wcfg, wout))) return r;
   return GR_OK;
 }
 
@@ -1712,6 +1862,26 @@ int gr_step_compact(gr_engine* e, const gr_cinbox* in, gr_coutbox* out) {
   memset(out, 0, sizeof(*out));
   const int r = gr_step_compact_begin(e, in);
   return r ? r : gr_step_compact_end(e, out);
+}
+
+int gr_step_compact_wire_out(gr_engine* e, const gr_cinbox* in, gr_coutbox* out, const gr_wire_out_cfg* cfg,
+                             gr_wire_out* wout) {
+  if (!e || !in || !out || !cfg || !wout || cfg->max_batch_msgs == 0) return GR_EINVAL;
+  std::lock_guard<std::mutex> guard(e->mu);  // held over the check and both halves, as gr_step_wire_out
+  GR_REFUSE_PENDING(e);
+  if (!e->nodes_cap || !e->n_targets) return GR_ESTATE;  // gr_bind_nodes and gr_bind_targets first
+  memset(out, 0, sizeof(*out));
+  memset(wout, 0, sizeof(*wout));
+  const int r = compact_begin_locked(e, in);
+  return r ? r : compact_end_locked(e, out, cfg, wout);
+}
+
+int gr_wire_out_host(const gr_message* msgs, size_t n, const uint64_t* cluster_ids, const uint64_t* node_ids,
+                     const uint64_t* remote_ids, uint32_t n_peers, uint32_t slots, const uint32_t* target_of,
+                     uint32_t n_targets, const gr_wire_out_cfg* cfg, struct grw_batch* batches, size_t* n_batches,
+                     struct grw_message* wmsgs, size_t* n_wmsgs, uint32_t* batch_target, uint8_t* held) {
+  return host::wire_out_host(msgs, n, cluster_ids, node_ids, remote_ids, n_peers, slots, target_of, n_targets, cfg,
+                             batches, n_batches, wmsgs, n_wmsgs, batch_target, held);
 }
 
 int gr_cinbox_reserve(gr_engine* e, size_t n_msgs, size_t n_ext_msgs, size_t n_locals, size_t n_ext_locals,

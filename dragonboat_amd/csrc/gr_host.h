@@ -8,6 +8,7 @@
 #include <cstring>
 #include <vector>
 
+#include "gpuraft_wire.h"
 #include "gr_layout.h"
 
 namespace gr {
@@ -735,6 +736,105 @@ __host__ __device__ inline void locals_to_rows(const gr_local_input& x, uint32_t
   *rhi = x.read_ctx_high;
   *rnd = x.rand;
   *lword = local_word(*ticks, *qticks, *prop, *lflags);
+}
+
+// ---- entry-free outbox mail by wire (gpuraft.h gr_step_wire_out). The rule
+// lives here once: gr_wire_out_host and the kernels of gr_io.h run these.
+// A message the device can finish alone: no entries (no payload from the host's
+// log) and no Snapshot.
+__host__ __device__ inline bool wire_out_msg_ok(const gr_message& m) {
+  return m.n_entries == 0 && m.type != GR_INSTALL_SNAPSHOT;
+}
+// What INTEGRATION.md's MessageOf builds for outbox record m of a peer with node
+// id `from` in cluster `cluster`, whose remote slot m.slot holds node id `to`.
+__host__ __device__ inline grw_message wire_out_record(const gr_message& m, uint64_t to, uint64_t from,
+                                                       uint64_t cluster, uint32_t batch) {
+  grw_message w{};  // decode-only fields, entry and snapshot fields, padding: 0
+  w.to = to;
+  w.from = from;
+  w.cluster_id = cluster;
+  w.term = m.term;
+  w.log_term = m.log_term;
+  w.log_index = m.log_index;
+  w.commit = m.commit;
+  w.hint = m.hint;
+  w.hint_high = m.hint_high;
+  w.batch = batch;
+  w.type = (int32_t)m.type;
+  w.reject = m.reject ? 1 : 0;
+  return w;
+}
+// Batch b of the pass: messages [first, first + n) of the message array.
+__host__ __device__ inline grw_batch wire_out_batch(const gr_wire_out_cfg& cfg, uint32_t first, uint32_t n) {
+  grw_batch b{};
+  b.deployment_id = cfg.deployment_id;
+  b.source_off = cfg.source_off;
+  b.source_len = cfg.source_len;
+  b.first_msg = first;
+  b.n_msgs = n;
+  b.bin_ver = cfg.bin_ver;
+  return b;
+}
+__host__ __device__ inline uint32_t wire_out_batches_of(uint32_t n, uint32_t max_batch_msgs) {
+  return n / max_batch_msgs + (n % max_batch_msgs ? 1u : 0u);
+}
+inline bool wire_out_args_ok(const uint32_t* target_of, size_t n_pairs, uint32_t n_targets,
+                             const gr_wire_out_cfg* cfg) {
+  if (n_targets == 0 || n_targets > GR_MAX_TARGETS || (n_pairs && !target_of)) return false;
+  if (cfg && cfg->max_batch_msgs == 0) return false;
+  for (size_t x = 0; x < n_pairs; ++x)
+    if (target_of[x] != GR_TARGET_HOST && target_of[x] >= n_targets) return false;
+  return true;
+}
+
+// gr_wire_out_host (gpuraft.h). Every output array has room for n records.
+inline int wire_out_host(const gr_message* msgs, size_t n, const uint64_t* cluster_ids, const uint64_t* node_ids,
+                         const uint64_t* remote_ids, uint32_t n_peers, uint32_t slots, const uint32_t* target_of,
+                         uint32_t n_targets, const gr_wire_out_cfg* cfg, grw_batch* batches, size_t* n_batches,
+                         grw_message* wmsgs, size_t* n_wmsgs, uint32_t* batch_target, uint8_t* held) {
+  if (!cfg || !n_batches || !n_wmsgs || slots == 0 || slots > GR_SMAX) return GR_EINVAL;
+  if (n && (!msgs || !cluster_ids || !node_ids || !remote_ids || !batches || !wmsgs || !batch_target || !held))
+    return GR_EINVAL;
+  if (n >= 0x80000000ull) return GR_EINVAL;
+  if (!wire_out_args_ok(target_of, (size_t)n_peers * slots, n_targets, cfg)) return GR_EINVAL;
+  for (size_t k = 0; k < n; ++k)
+    if (msgs[k].peer >= n_peers || msgs[k].slot >= slots) return GR_EINVAL;
+  // a mailbox = a run of records with one (peer, slot); all of it goes one way
+  std::vector<uint32_t> tcount(n_targets, 0);
+  for (size_t a = 0; a < n;) {
+    size_t b = a;
+    bool ok = true;
+    while (b < n && msgs[b].peer == msgs[a].peer && msgs[b].slot == msgs[a].slot) ok = wire_out_msg_ok(msgs[b++]) && ok;
+    const uint32_t t = target_of[(size_t)msgs[a].peer * slots + msgs[a].slot];
+    const bool wire = ok && t != GR_TARGET_HOST;
+    for (size_t k = a; k < b; ++k) held[k] = wire ? 0 : 1;
+    if (wire) tcount[t] += (uint32_t)(b - a);
+    a = b;
+  }
+  // outbox order is (sender, remote slot, position): a stable sort by target on top
+  std::vector<uint32_t> tbase(n_targets + 1, 0), tbatch(n_targets + 1, 0);
+  for (uint32_t t = 0; t < n_targets; ++t) {
+    tbase[t + 1] = tbase[t] + tcount[t];
+    tbatch[t + 1] = tbatch[t] + wire_out_batches_of(tcount[t], cfg->max_batch_msgs);
+  }
+  std::vector<uint32_t> at(tbase.begin(), tbase.end() - 1);
+  for (size_t k = 0; k < n; ++k) {
+    if (held[k]) continue;
+    const gr_message& m = msgs[k];
+    const uint32_t t = target_of[(size_t)m.peer * slots + m.slot], pos = at[t]++;
+    wmsgs[pos] = wire_out_record(m, remote_ids[(size_t)m.peer * slots + m.slot], node_ids[m.peer],
+                                 cluster_ids[m.peer], tbatch[t] + (pos - tbase[t]) / cfg->max_batch_msgs);
+  }
+  for (uint32_t t = 0; t < n_targets; ++t)
+    for (uint32_t b = tbatch[t]; b < tbatch[t + 1]; ++b) {
+      const uint32_t first = tbase[t] + (b - tbatch[t]) * cfg->max_batch_msgs;
+      const uint32_t left = tbase[t + 1] - first;
+      batches[b] = wire_out_batch(*cfg, first, left < cfg->max_batch_msgs ? left : cfg->max_batch_msgs);
+      batch_target[b] = t;
+    }
+  *n_wmsgs = tbase[n_targets];
+  *n_batches = tbatch[n_targets];
+  return GR_OK;
 }
 
 }  // namespace host

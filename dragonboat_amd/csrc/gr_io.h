@@ -20,6 +20,9 @@
 //              last one given wins, zero rows for lanes without one)
 //   outbox: out_counts -> exclusive scan -> pack_outbox (lane, slot, arrival order)
 //           pack_results (one gr_peer_result per lane)
+//           gr_step_wire_out: wire_out_group -> scan -> wire_out_plan ->
+//           wire_out_scatter + wire_out_batches (entry-free mailboxes as
+//           grw_message / grw_batch records by send queue; the compact pack skips them)
 //
 // Routes are RT_IDENTITY both ways (mailbox j*nl + lane), so no route table is
 // built or read. The codec functions are the same ones the test-only host
@@ -377,15 +380,19 @@ __device__ inline void mailbox_records(const Mailbox& mb, uint32_t peer, uint32_
 // Per lane: records (high word) and those needing an ext record (low word) in
 // one u64, so one scan gives both output offsets; rx = 1 when the result needs
 // the full record.
+// wf (gr_step_wire_out; nullptr otherwise): wf[j * nl + l] != 0 marks a mailbox
+// that left by wire, which the compact outbox skips.
 __global__ void out_counts_c(SpaceView out, LaneBase L, StateBase st, uint32_t nl, uint32_t S, uint64_t* oc,
-                             uint32_t* rx) {
+                             uint32_t* rx, const uint8_t* wf) {
   for (uint32_t l = io_tid(); l < nl; l += io_stride()) {
     uint32_t c = 0, e = 0;
-    for (uint32_t j = 0; j < S; ++j)
+    for (uint32_t j = 0; j < S; ++j) {
+      if (wf && wf[j * nl + l]) continue;  // left by wire
       mailbox_records(out.at(j * nl + l), 0u, j, [&](const gr_cmsg&, const gr_message* full) {
         ++c;
         e += full ? 1u : 0u;
       });
+    }
     oc[l] = ((uint64_t)c << 32) | e;
     gr_cresult cr;
     rx[l] = host::result_needs_ext(L.u8(LR_RFLAGS)[l]) || !host::cresult_of(host::make_result(L, st, l, 0), &cr)
@@ -404,11 +411,12 @@ __global__ void finish_total_c(const uint64_t* oc, const uint64_t* off, const ui
 }
 
 __global__ void pack_outbox_c(SpaceView out, uint32_t nl, uint32_t S, const uint64_t* off, const uint32_t* peer_of_lane,
-                              gr_cmsg* rec, gr_message* ext) {
+                              gr_cmsg* rec, gr_message* ext, const uint8_t* wf) {
   for (uint32_t l = io_tid(); l < nl; l += io_stride()) {
     uint32_t o = (uint32_t)(off[l] >> 32), eo = (uint32_t)off[l];
     const uint32_t peer = peer_of_lane[l];
-    for (uint32_t j = 0; j < S; ++j)
+    for (uint32_t j = 0; j < S; ++j) {
+      if (wf && wf[j * nl + l]) continue;  // left by wire
       mailbox_records(out.at(j * nl + l), peer, j, [&](gr_cmsg cm, const gr_message* full) {
         if (full) {
           cm.flags = GR_CM_EXT;
@@ -417,6 +425,7 @@ __global__ void pack_outbox_c(SpaceView out, uint32_t nl, uint32_t S, const uint
         }
         rec[o++] = cm;
       });
+    }
   }
 }
 
@@ -432,6 +441,179 @@ __global__ void pack_results_c(LaneBase L, StateBase st, const uint32_t* peer_of
       ext[roff[l]] = pr;
     }
     out[l] = c;
+  }
+}
+
+// ---- entry-free outbox mail by wire (gpuraft.h gr_step_wire_out; the rule is
+// gr_host.h wire_out_*). The out mailboxes that may leave as MessageBatch records
+// are grouped by send queue without an atomic on a shared word: workgroup b owns
+// lanes [256 b, 256 b + 256), counts its messages per target into
+// cnt[t * nblk + b], one exclusive scan of that target-major matrix gives every
+// (target, workgroup) its base, and a mailbox's place inside its workgroup's
+// share is its rank: the messages of lower lanes (then lower remote slots) of the
+// workgroup to the same target. Message order is therefore target, sending
+// lane (= engine slot, lanes ascend with it), remote slot, mailbox position.
+constexpr uint32_t kWoWaves = kIoBlock / 64;
+static_assert(GR_MAX_TARGETS <= kIoBlock, "one thread per target writes a workgroup's counts");
+
+// Classify and rank. wf[j * nl + l] = messages of mailbox (l, j) when it goes by
+// wire, else 0. A uniform mailbox is decided from its count byte (accepts go;
+// Replicates go when no entry bit is set); any other from its decoded messages.
+// Each wave takes the targets its lanes hold one at a time (a wave-uniform loop):
+// the lanes with mail for that target scan their counts with shuffles, the wave's
+// total goes to LDS, and after the barrier every mailbox adds the totals of the
+// waves below its own.
+template <int S>
+__global__ __launch_bounds__(kIoBlock) void wire_out_group(SpaceView out, uint32_t nl, const uint32_t* peer_of_lane,
+                                                           const uint32_t* target_of, uint32_t T, uint8_t* wf,
+                                                           uint32_t* rank, uint32_t* cnt) {
+  __shared__ uint32_t wtot[kWoWaves][GR_MAX_TARGETS];
+  const uint32_t tid = threadIdx.x, w = tid >> 6, lane = tid & 63, nblk = gridDim.x;
+  for (uint32_t k = 0; k < kWoWaves; ++k)
+    if (tid < GR_MAX_TARGETS) wtot[k][tid] = 0;
+  const uint32_t l = blockIdx.x * kIoBlock + tid;
+  uint32_t tj[S], nj[S], rj[S], pend = 0;
+#pragma unroll
+  for (int j = 0; j < S; ++j) tj[j] = nj[j] = rj[j] = 0;
+  if (l < nl) {
+    const uint32_t peer = peer_of_lane[l];
+#pragma unroll
+    for (int j = 0; j < S; ++j) {
+      const Mailbox mb = out.at((uint32_t)j * nl + l);
+      const uint32_t cb = mb.cnt(), x = mb_n(cb), c = x < (uint32_t)GR_C ? x : (uint32_t)GR_C;
+      const uint32_t t = target_of[(uint64_t)peer * S + j];
+      bool ok = c != 0 && t != GR_TARGET_HOST;
+      if (ok) {
+        if (cb & MB_UNIFORM) {
+          ok = (cb & MB_RESP) || ((cb >> MB_N1_SHIFT) & ((1u << c) - 1u)) == 0;
+        } else {
+          for (uint32_t k = 0; k < c; ++k) ok = host::wire_out_msg_ok(host::decode_msg(mb, k)) && ok;
+        }
+      }
+      tj[j] = t;
+      nj[j] = ok ? c : 0u;
+      pend |= ok ? 1u << j : 0u;
+      wf[(uint64_t)j * nl + l] = (uint8_t)nj[j];
+    }
+  }
+  __syncthreads();
+  for (;;) {
+    const uint64_t bal = __ballot(pend != 0);
+    if (!bal) break;
+    uint32_t mine = 0;
+#pragma unroll
+    for (int j = S - 1; j >= 0; --j) mine = ((pend >> j) & 1u) ? tj[j] : mine;
+    const uint32_t t = (uint32_t)__shfl((int)mine, __ffsll((unsigned long long)bal) - 1);
+    uint32_t c = 0, m = 0;
+#pragma unroll
+    for (int j = 0; j < S; ++j)
+      if (((pend >> j) & 1u) && tj[j] == t) {
+        rj[j] = c;
+        c += nj[j];
+        m |= 1u << j;
+      }
+    pend &= ~m;
+    uint32_t x = c;
+#pragma unroll
+    for (uint32_t d = 1; d < 64; d <<= 1) {
+      const uint32_t y = (uint32_t)__shfl_up((int)x, d);
+      if (lane >= d) x += y;
+    }
+    const uint32_t tot = (uint32_t)__shfl((int)x, 63);
+#pragma unroll
+    for (int j = 0; j < S; ++j) rj[j] += ((m >> j) & 1u) ? x - c : 0u;
+    if (lane == 0) wtot[w][t] = tot;  // t < T: gr_bind_targets checked every index
+  }
+  __syncthreads();
+  if (l < nl) {
+#pragma unroll
+    for (int j = 0; j < S; ++j)
+      if (nj[j]) {
+        uint32_t o = 0;
+        for (uint32_t k = 0; k < kWoWaves; ++k) o += k < w ? wtot[k][tj[j]] : 0u;
+        rank[(uint64_t)j * nl + l] = rj[j] + o;
+      }
+  }
+  if (tid < T) {
+    uint32_t s = 0;
+    for (uint32_t k = 0; k < kWoWaves; ++k) s += wtot[k][tid];
+    cnt[(uint64_t)tid * nblk + blockIdx.x] = s;
+  }
+}
+
+// One workgroup: per target its first message and first batch (plan[t] and
+// plan[T + 1 + t], t <= T: the last of each is the total), from the scanned count
+// matrix; totals[0..1] = messages, batches (one D2H).
+__global__ __launch_bounds__(kIoBlock) void wire_out_plan(const uint32_t* cnt, const uint32_t* base, uint32_t T,
+                                                          uint32_t nblk, uint32_t mbm, uint32_t* plan,
+                                                          uint32_t* totals) {
+  __shared__ uint32_t lds4[kIoBlock / 64];
+  const uint32_t tid = threadIdx.x;
+  const uint64_t last = (uint64_t)T * nblk - 1;
+  const uint32_t total = base[last] + cnt[last];
+  uint32_t first = 0, n = 0;
+  if (tid < T) {
+    first = base[(uint64_t)tid * nblk];
+    n = (tid + 1 < T ? base[(uint64_t)(tid + 1) * nblk] : total) - first;
+  }
+  uint32_t nb;
+  const uint32_t b0 = scan::block_excl_scan(host::wire_out_batches_of(n, mbm), lds4, &nb);
+  if (tid < T) {
+    plan[tid] = first;
+    plan[T + 1 + tid] = b0;
+  }
+  if (tid == 0) {
+    plan[T] = total;
+    plan[2 * T + 1] = nb;
+    totals[0] = total;
+    totals[1] = nb;
+  }
+}
+
+// The batch table: batch b belongs to the target t with plan batch[t] <= b < batch[t + 1].
+__global__ void wire_out_batches(const uint32_t* plan, uint32_t T, gr_wire_out_cfg cfg, uint32_t nb,
+                                 grw_batch* batches, uint32_t* batch_target) {
+  const uint32_t* tbase = plan;
+  const uint32_t* tbatch = plan + T + 1;
+  for (uint32_t b = io_tid(); b < nb; b += io_stride()) {
+    uint32_t lo = 0, hi = T;  // the first t in [0, T) with tbatch[t + 1] > b (it exists: b < tbatch[T])
+    while (lo + 1 < hi) {
+      const uint32_t mid = (lo + hi) / 2;
+      if (tbatch[mid] <= b) lo = mid;
+      else hi = mid;
+    }
+    const uint32_t t = lo;
+    const uint32_t first = tbase[t] + (b - tbatch[t]) * cfg.max_batch_msgs, left = tbase[t + 1] - first;
+    batches[b] = host::wire_out_batch(cfg, first, left < cfg.max_batch_msgs ? left : cfg.max_batch_msgs);
+    batch_target[b] = t;
+  }
+}
+
+// Scatter: every wire mailbox writes its records at base[t][workgroup] + rank
+// (the same lane-to-workgroup map as wire_out_group: launch it with that grid).
+template <int S>
+__global__ __launch_bounds__(kIoBlock) void wire_out_scatter(SpaceView out, uint32_t nl, const uint32_t* peer_of_lane,
+                                                             const uint32_t* target_of, StateBase st,
+                                                             const uint64_t* cluster_of, const uint8_t* wf,
+                                                             const uint32_t* rank, const uint32_t* base,
+                                                             const uint32_t* plan, uint32_t T, uint32_t mbm,
+                                                             grw_message* wmsgs) {
+  using Rw = Rows<S>;
+  const uint32_t l = blockIdx.x * kIoBlock + threadIdx.x, nblk = gridDim.x;
+  if (l >= nl) return;
+  const uint32_t peer = peer_of_lane[l];
+  const uint64_t from = st.u64(SR_NODE_ID)[peer], cluster = cluster_of[peer];
+#pragma unroll
+  for (int j = 0; j < S; ++j) {
+    const uint32_t n = wf[(uint64_t)j * nl + l];
+    if (!n) continue;
+    const Mailbox mb = out.at((uint32_t)j * nl + l);
+    const uint32_t t = target_of[(uint64_t)peer * S + j];
+    const uint32_t pos = base[(uint64_t)t * nblk + blockIdx.x] + rank[(uint64_t)j * nl + l];
+    const uint64_t to = st.u64(Rw::RID + j)[peer];
+    for (uint32_t k = 0; k < n; ++k)
+      wmsgs[pos + k] = host::wire_out_record(host::decode_msg(mb, k), to, from, cluster,
+                                             plan[T + 1 + t] + (pos + k - plan[t]) / mbm);
   }
 }
 

@@ -158,6 +158,17 @@ def load_library(path=LIB_PATH):
         lib.gr_splitmix64.restype = c.c_uint64
     if hasattr(lib, "gr_steady_wave_uniform"):  # (older builds loaded for A/B runs lack it)
         lib.gr_steady_wave_uniform.argtypes = [c.c_void_p]
+    if hasattr(lib, "gr_bind_targets"):  # (older builds loaded for A/B runs lack the outbound wire path)
+        lib.gr_bind_targets.argtypes = [c.c_void_p, c.c_void_p, c.c_uint32, c.c_uint32]
+        lib.gr_step_wire_out.argtypes = [c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p, c.c_size_t, c.c_void_p,
+                                         c.c_size_t, c.POINTER(abi.COutbox), c.POINTER(abi.WireUnrouted),
+                                         c.POINTER(abi.WireOutCfg), c.POINTER(abi.WireOut)]
+        lib.gr_step_compact_wire_out.argtypes = [c.c_void_p, c.POINTER(abi.CInbox), c.POINTER(abi.COutbox),
+                                                 c.POINTER(abi.WireOutCfg), c.POINTER(abi.WireOut)]
+        lib.gr_wire_out_host.argtypes = [c.c_void_p, c.c_size_t, c.c_void_p, c.c_void_p, c.c_void_p, c.c_uint32,
+                                         c.c_uint32, c.c_void_p, c.c_uint32, c.POINTER(abi.WireOutCfg), c.c_void_p,
+                                         c.POINTER(c.c_size_t), c.c_void_p, c.POINTER(c.c_size_t), c.c_void_p,
+                                         c.c_void_p]
     if path == LIB_PATH:
         _lib = lib
     _libs[path] = lib
@@ -166,7 +177,59 @@ def load_library(path=LIB_PATH):
 
 def _check(rc, what):
     if rc != 0:
-        raise GpuRaftError(f"{what}: {load_library().gr_strerror(rc).decode()} ({rc})")
+        err = GpuRaftError(f"{what}: {load_library().gr_strerror(rc).decode()} ({rc})")
+        err.rc = rc
+        raise err
+
+
+def wire_out_cfg(cfg):
+    """An abi.WireOutCfg from one, or from a mapping of its fields (gpuraft.h gr_wire_out_cfg)."""
+    if isinstance(cfg, abi.WireOutCfg):
+        return cfg
+    return abi.WireOutCfg(**{k: int(v) for k, v in dict(cfg).items()})
+
+
+class WireOut:
+    """What gr_step_wire_out left for grw_encode_device: device pointers of the
+    grw_batch / grw_message records (engine-owned, valid until the engine's next
+    stepping call) and a host copy of batch_target."""
+
+    def __init__(self, wo):
+        self.d_batches, self.n_batches = wo.d_batches or 0, wo.n_batches
+        self.d_msgs, self.n_msgs = wo.d_msgs or 0, wo.n_msgs
+        self.batch_target = np.zeros(wo.n_batches, np.uint32)
+        if wo.n_batches:
+            ctypes.memmove(self.batch_target.ctypes.data, wo.batch_target, wo.n_batches * 4)
+
+
+def wire_out_host(msgs, cluster_ids, node_ids, remote_ids, target_of, n_targets, cfg, slots=None, lib=None):
+    """gr_wire_out_host: the outbound wire rule on the CPU (no engine, no GPU).
+    msgs: full outbox records in outbox order; cluster_ids / node_ids [n_peers],
+    remote_ids / target_of [n_peers, slots]. Returns (batches, wire messages,
+    batch_target, held flags); raises GpuRaftError on a refusal."""
+    from . import wire as W
+    lib = lib or load_library()
+    msgs = np.ascontiguousarray(msgs, abi.MESSAGE)
+    cl = np.ascontiguousarray(cluster_ids, np.uint64)
+    nd = np.ascontiguousarray(node_ids, np.uint64)
+    target_of = np.asarray(target_of, np.uint32)
+    slots = target_of.shape[1] if slots is None else slots
+    rid = np.ascontiguousarray(np.asarray(remote_ids, np.uint64)[:, :slots])
+    tg = np.ascontiguousarray(target_of)
+    n = len(msgs)
+    bat = np.zeros(n, W.BATCH)
+    wm = np.zeros(n, W.WMESSAGE)
+    bt = np.zeros(n, np.uint32)
+    held = np.zeros(n, np.uint8)
+    nb, nw = ctypes.c_size_t(), ctypes.c_size_t()
+    c = wire_out_cfg(cfg)
+
+    def ptr(a):
+        return a.ctypes.data if a.size else None
+    _check(lib.gr_wire_out_host(ptr(msgs), n, ptr(cl), ptr(nd), ptr(rid), len(cl), slots, ptr(tg), n_targets,
+                                ctypes.byref(c), ptr(bat), ctypes.byref(nb), ptr(wm), ctypes.byref(nw), ptr(bt),
+                                ptr(held)), "gr_wire_out_host")
+    return bat[:nb.value].copy(), wm[:nw.value].copy(), bt[:nb.value].copy(), held.astype(bool)
 
 
 class Engine:
@@ -454,13 +517,39 @@ class Engine:
         _check(self.lib.gr_bind_nodes(self._h, cl.ctypes.data if len(cl) else None,
                                       nd.ctypes.data if len(nd) else None, len(cl)), "gr_bind_nodes")
 
-    def step_wire(self, d_msgs, n_msgs, d_ents, n_ents, locals_=None, compact=False):
+    def bind_targets(self, target_of, n_targets):
+        """gr_bind_targets: target_of[p, j] is the send queue of engine slot p's
+        remote slot j (abi.TARGET_HOST: that pair's mail stays with the host)."""
+        t = np.ascontiguousarray(target_of, np.uint32)
+        assert t.ndim == 2 and t.shape[1] == self.slots
+        _check(self.lib.gr_bind_targets(self._h, t.ctypes.data if t.size else None, t.shape[0], n_targets),
+               "gr_bind_targets")
+
+    wire_out_host = staticmethod(wire_out_host)
+
+    def step_wire(self, d_msgs, n_msgs, d_ents, n_ents, locals_=None, compact=False, wire_out=None):
         """gr_step_wire over decoded wire records already in HBM (device pointers, as
         grw_decode_device leaves them). Returns (messages, results, unrouted
         indices, unrouted reasons); with compact=True gr_step_wire_compact, whose
         outbox is returned as step_compact returns it: ((cmsgs, ext msgs, cresults,
-        ext results), unrouted indices, unrouted reasons)."""
+        ext results), unrouted indices, unrouted reasons). wire_out=cfg (an
+        abi.WireOutCfg or a mapping of its fields): gr_step_wire_out, the compact
+        return with a WireOut appended; the entry-free mailboxes are in it and not
+        in the compact outbox."""
         locals_ = np.zeros(0, abi.LOCAL) if locals_ is None else np.ascontiguousarray(locals_, abi.LOCAL)
+        if wire_out is not None:
+            ob, un, wo, cfg = abi.COutbox(), abi.WireUnrouted(), abi.WireOut(), wire_out_cfg(wire_out)
+            _check(self.lib.gr_step_wire_out(self._h, d_msgs, n_msgs, d_ents, n_ents,
+                                             locals_.ctypes.data if len(locals_) else None, len(locals_),
+                                             ctypes.byref(ob), ctypes.byref(un), ctypes.byref(cfg), ctypes.byref(wo)),
+                   "gr_step_wire_out")
+            idx = np.zeros(un.n, np.uint32)
+            why = np.zeros(un.n, np.uint8)
+            if un.n:
+                ctypes.memmove(idx.ctypes.data, un.index, un.n * 4)
+                ctypes.memmove(why.ctypes.data, un.reason, un.n)
+            w = WireOut(wo)
+            return self._take_coutbox(ob), idx, why, w
         ob = abi.COutbox() if compact else abi.Outbox()
         un = abi.WireUnrouted()
         fn = self.lib.gr_step_wire_compact if compact else self.lib.gr_step_wire
@@ -521,12 +610,19 @@ class Engine:
                                        ctypes.byref(nx)), "gr_pack_locals")
         return c, ext[:nx.value].copy()
 
-    def step_compact(self, cmsgs, ext_msgs, clocals, ext_locals, halves=False):
+    def step_compact(self, cmsgs, ext_msgs, clocals, ext_locals, halves=False, wire_out=None):
         """One synchronous pass with compact records (gr_step_compact, or with
         halves=True its two halves gr_step_compact_begin + _end). Returns
-        (cmsgs, ext msgs, cresults, ext results) copied out of the engine's outbox."""
+        (cmsgs, ext msgs, cresults, ext results) copied out of the engine's outbox.
+        wire_out=cfg: gr_step_compact_wire_out; returns (that tuple, WireOut)."""
         ib = abi.cinbox_of(cmsgs, ext_msgs, clocals, ext_locals)
         ob = abi.COutbox()
+        if wire_out is not None:
+            wo, cfg = abi.WireOut(), wire_out_cfg(wire_out)
+            _check(self.lib.gr_step_compact_wire_out(self._h, ctypes.byref(ib), ctypes.byref(ob), ctypes.byref(cfg),
+                                                     ctypes.byref(wo)), "gr_step_compact_wire_out")
+            w = WireOut(wo)
+            return self._take_coutbox(ob), w
         if halves:
             _check(self.lib.gr_step_compact_begin(self._h, ctypes.byref(ib)), "gr_step_compact_begin")
             _check(self.lib.gr_step_compact_end(self._h, ctypes.byref(ob)), "gr_step_compact_end")

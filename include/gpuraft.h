@@ -496,7 +496,8 @@ int gr_step_compact(gr_engine* e, const gr_cinbox* in, gr_coutbox* out);
  * gr_step_device, gr_load_* / gr_sync_*, gr_set_locals, gr_bind_routes,
  * gr_compact_log, gr_commit_update, gr_apply_config_change, gr_restore_remotes, gr_notify_applied,
  * gr_set_snapshot_recs, gr_get_snapshot_recs, gr_restored_snapshots, gr_set_cc_indexes,
- * gr_get_cc_indexes, gr_collect_results,
+ * gr_get_cc_indexes, gr_collect_results, gr_bind_nodes, gr_bind_targets,
+ * gr_step_wire, gr_step_wire_compact, gr_step_wire_out, gr_step_compact_wire_out,
  * gr_space_cold_used) returns GR_ESTATE and changes nothing. */
 int gr_step_compact_begin(gr_engine* e, const gr_cinbox* in);
 int gr_step_compact_end(gr_engine* e, gr_coutbox* out);
@@ -963,6 +964,100 @@ int gr_step_wire(gr_engine* e, const struct grw_message* d_msgs, size_t n_msgs, 
 int gr_step_wire_compact(gr_engine* e, const struct grw_message* d_msgs, size_t n_msgs,
                          const struct grw_entry* d_ents, size_t n_ents, const gr_local_input* locals,
                          size_t n_locals, gr_coutbox* out, gr_wire_unrouted* unrouted);
+/*
+ * Frames straight out of the step: the pass's entry-free outbox mail leaves as
+ * grw_batch / grw_message records in HBM, ready for grw_encode_device
+ * (gpuraft_wire.h), so for that mail only the frames and one target index per
+ * batch cross PCIe. It replaces, for those messages, the host building a
+ * pb.Message per record, queueing it per target address (Transport.ASyncSend,
+ * internal/transport/transport.go:343-397) and cutting the queue into
+ * MessageBatches (Transport.processQueue, transport.go:399-476, whose batching
+ * "is largely for heartbeat messages as entries are already batched",
+ * transport.go:430-433).
+ *
+ * gr_bind_targets: target_of[p * slots + j] (slots = gr_config.slots, whatever
+ * slot count the engine instantiates for it) is the send queue (one per
+ * destination address, as the reference keys them) of engine slot p's remote
+ * slot j, below n_targets, or GR_TARGET_HOST: this pair's mail stays with the
+ * host. Slots at and above n_peers get GR_TARGET_HOST. n_targets is 1 ..
+ * GR_MAX_TARGETS: the device groups by target with one counter per workgroup and
+ * target and no atomics, which bounds the count. GR_EINVAL for an index at or
+ * above n_targets, n_peers above max_peers, n_targets 0 or above the maximum;
+ * GR_ESTATE while a gr_step_compact_begin is pending (as gr_bind_nodes).
+ * gr_bind_nodes also keeps the cluster id of every slot for the records' ClusterID.
+ *
+ * The rule. The unit is the out mailbox, the messages of one sending peer to
+ * one remote slot: order matters only inside a (sender, receiver) pair, and
+ * all-or-nothing keeps it on both routes. A mailbox goes by wire when its pair
+ * has a target, every message in it has n_entries == 0 and none is
+ * GR_INSTALL_SNAPSHOT; otherwise the whole mailbox is held and appears in the
+ * gr_coutbox exactly as gr_step_compact / gr_step_wire_compact return it (same
+ * records, ext records and order; results are those of every lane, unchanged).
+ * An escalated lane's prefix messages follow the same rule. With config-change
+ * entries on, marks exist only on Replicates with entries, which are held.
+ *
+ * The wire record is INTEGRATION.md's MessageOf: to = the remote id of the slot,
+ * from = the sender's node id, cluster_id = the bound cluster; type, term,
+ * log_term, log_index, commit, hint, hint_high copied; reject 0 or 1;
+ * n_entries, first_entry, snapshot_len, snapshot_off 0; batch = its batch;
+ * decode-only fields and padding 0. Messages are ordered by target, then
+ * sending engine slot, then remote slot, then mailbox position. Every target
+ * with n messages gets ceil(n / max_batch_msgs) consecutive batches, all but
+ * the last full, targets ascending; a target without mail gets none. A batch
+ * record holds cfg's deployment_id, bin_ver, source_off, source_len, its
+ * first_msg and n_msgs, and 0 elsewhere. (The reference's own cut depends on
+ * timing; MarshalTo of a given batch is the bit-exact part.)
+ *
+ * gr_step_wire_out = gr_step_wire_compact, gr_step_compact_wire_out =
+ * gr_step_compact, plus cfg and wout. Both need gr_bind_nodes and
+ * gr_bind_targets first (GR_ESTATE), and max_batch_msgs >= 1 (GR_EINVAL): the
+ * host picks it so that max_batch_msgs entry-free messages stay below its
+ * rpcMaxMsgSize. source_off / source_len name the SourceAddress bytes in the
+ * payload buffer the caller hands to grw_encode_device. wout's device arrays are
+ * engine-owned, complete when the call returns and valid until the engine's next
+ * stepping call; d_batches is writable (the encoder fills frame_off and
+ * frame_len); batch_target is pinned host memory, n_batches values.
+ *
+ * gr_wire_out_host applies the same rule and order on the CPU (no engine; the
+ * code is shared with the kernels): msgs are full outbox records in outbox
+ * order (a mailbox is a run of records with one peer and slot); cluster_ids and
+ * node_ids hold n_peers values, remote_ids and target_of n_peers * slots.
+ * batches, wmsgs, batch_target and held have room for n records; held[k] = 1
+ * when record k stays. GR_EINVAL, with nothing written, for a null array, a
+ * record's peer or slot out of range, and gr_bind_targets' refusals.
+ *
+ * Out of scope: the _begin/_end halves, the full-record gr_step and
+ * gr_step_wire, gr_step_device and graphs, entry-carrying messages and
+ * InstallSnapshot all keep their records.
+ */
+#define GR_TARGET_HOST 0xFFFFFFFFu
+#define GR_MAX_TARGETS 256
+typedef struct gr_wire_out_cfg {
+  uint64_t deployment_id;
+  uint64_t source_off;
+  uint32_t source_len;
+  uint32_t bin_ver;
+  uint32_t max_batch_msgs;
+  uint32_t pad;
+} gr_wire_out_cfg;
+struct grw_batch;
+typedef struct gr_wire_out {
+  struct grw_batch* d_batches;      /* device */
+  size_t n_batches;
+  const struct grw_message* d_msgs; /* device */
+  size_t n_msgs;
+  const uint32_t* batch_target;     /* pinned host */
+} gr_wire_out;
+int gr_bind_targets(gr_engine* e, const uint32_t* target_of, uint32_t n_peers, uint32_t n_targets);
+int gr_step_wire_out(gr_engine* e, const struct grw_message* d_msgs, size_t n_msgs, const struct grw_entry* d_ents,
+                     size_t n_ents, const gr_local_input* locals, size_t n_locals, gr_coutbox* out,
+                     gr_wire_unrouted* unrouted, const gr_wire_out_cfg* cfg, gr_wire_out* wout);
+int gr_step_compact_wire_out(gr_engine* e, const gr_cinbox* in, gr_coutbox* out, const gr_wire_out_cfg* cfg,
+                             gr_wire_out* wout);
+int gr_wire_out_host(const gr_message* msgs, size_t n, const uint64_t* cluster_ids, const uint64_t* node_ids,
+                     const uint64_t* remote_ids, uint32_t n_peers, uint32_t slots, const uint32_t* target_of,
+                     uint32_t n_targets, const gr_wire_out_cfg* cfg, struct grw_batch* batches, size_t* n_batches,
+                     struct grw_message* wmsgs, size_t* n_wmsgs, uint32_t* batch_target, uint8_t* held);
 /* Decode the messages of a device space into gr_message records (testing). A
  * mailbox whose cold fields were lost in the exchange (MB_COLD_LOST) decodes to
  * records with reject = 0xFF and no other field. */
