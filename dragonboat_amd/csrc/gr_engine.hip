@@ -12,8 +12,8 @@
 #include <mutex>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
-
 
 #include "gr_host.h"
 #include "gr_io.h"
@@ -22,47 +22,44 @@
 
 namespace gr {
 
+#ifdef GR_COVERAGE
+#define GR_EXTERN_COVER(SS) extern template hipError_t cover_read<SS>(uint32_t, uint64_t*);
+#else
+#define GR_EXTERN_COVER(SS)
+#endif
 #define GR_EXTERN_SLOTS(SS)                                                                                  \
   extern template hipError_t launch<SS>(const StepParams&, uint32_t*, uint32_t*, uint32_t, uint32_t, hipStream_t, \
-                                        const PassTiming*, bool);
+                                        const PassTiming*, bool);                                            \
+  GR_EXTERN_COVER(SS)
 GR_EXTERN_SLOTS(1)
 GR_EXTERN_SLOTS(3)
 GR_EXTERN_SLOTS(5)
 GR_EXTERN_SLOTS(8)
-#ifdef GR_COVERAGE
-extern template hipError_t cover_read<1>(uint64_t*);
-extern template hipError_t cover_read<3>(uint64_t*);
-extern template hipError_t cover_read<5>(uint64_t*);
-extern template hipError_t cover_read<8>(uint64_t*);
-extern template hipError_t cover_elect_read<1>(uint64_t*);
-extern template hipError_t cover_elect_read<3>(uint64_t*);
-extern template hipError_t cover_elect_read<5>(uint64_t*);
-extern template hipError_t cover_elect_read<8>(uint64_t*);
-extern template hipError_t cover_quiesce_read<1>(uint64_t*);
-extern template hipError_t cover_quiesce_read<3>(uint64_t*);
-extern template hipError_t cover_quiesce_read<5>(uint64_t*);
-extern template hipError_t cover_quiesce_read<8>(uint64_t*);
-extern template hipError_t cover_snap_read<1>(uint64_t*);
-extern template hipError_t cover_snap_read<3>(uint64_t*);
-extern template hipError_t cover_snap_read<5>(uint64_t*);
-extern template hipError_t cover_snap_read<8>(uint64_t*);
-extern template hipError_t cover_cc_read<1>(uint64_t*);
-extern template hipError_t cover_cc_read<3>(uint64_t*);
-extern template hipError_t cover_cc_read<5>(uint64_t*);
-extern template hipError_t cover_cc_read<8>(uint64_t*);
-#endif
+
+// with_slots(S, f): f(std::integral_constant<int, N>{}) for the instantiated
+// slot count N == S (instantiated_slots), so a kernel template is named once;
+// any other S is GR_EINVAL, or hipErrorInvalidValue where f returns hipError_t.
+static_assert(GR_SMAX == 8, "with_slots and instantiated_slots list the instantiated slot counts");
+static inline gr_error no_such_slots(gr_error) { return GR_EINVAL; }
+static inline hipError_t no_such_slots(hipError_t) { return hipErrorInvalidValue; }
+template <class F>
+static auto with_slots(uint32_t S, F&& f) -> decltype(f(std::integral_constant<int, 1>{})) {
+  switch (S) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    case 5: return f(std::integral_constant<int, 5>{});
+    case 8: return f(std::integral_constant<int, 8>{});
+  }
+  return no_such_slots(decltype(f(std::integral_constant<int, 1>{})){});
+}
 
 // tick_lanes: launch the tick kernel (some lane may carry ticks or a ReadIndex).
 static hipError_t launch_slots(uint32_t S, const StepParams& kp, uint32_t* bail_list, uint32_t* counters,
                                uint32_t list_cap, uint32_t parity, hipStream_t s, const PassTiming* t,
                                bool tick_lanes = true) {
-  switch (S) {
-    case 1: return launch<1>(kp, bail_list, counters, list_cap, parity, s, t, tick_lanes);
-    case 3: return launch<3>(kp, bail_list, counters, list_cap, parity, s, t, tick_lanes);
-    case 5: return launch<5>(kp, bail_list, counters, list_cap, parity, s, t, tick_lanes);
-    case 8: return launch<8>(kp, bail_list, counters, list_cap, parity, s, t, tick_lanes);
-  }
-  return hipErrorInvalidValue;
+  return with_slots(S, [&](auto ss) {
+    return launch<decltype(ss)::value>(kp, bail_list, counters, list_cap, parity, s, t, tick_lanes);
+  });
 }
 
 static uint32_t instantiated_slots(uint32_t want) {
@@ -77,6 +74,48 @@ static uint32_t instantiated_slots(uint32_t want) {
 
 using namespace gr;
 using namespace gr::host;
+
+#ifndef GR_INBOX_WC
+#define GR_INBOX_WC 1
+#endif
+// Pinned memory the host reads (outboxes) is plain; the inboxes the host only
+// writes and the device reads once are write-combined (no snooping of dirty
+// host cache lines during the upload).
+static const unsigned kInboxPinned =
+    GR_INBOX_WC ? (hipHostMallocDefault | hipHostMallocWriteCombined) : hipHostMallocDefault;
+
+// A device buffer (Buf) or a pinned host one (Pinned), grown on demand, reused,
+// and freed with its engine; the contents do not survive a grow.
+template <bool kPinned>
+struct GrowBuf {
+  uint8_t* p = nullptr;
+  size_t n = 0;
+  const unsigned flags = hipHostMallocDefault;  // of a pinned buffer
+  GrowBuf() = default;
+  explicit GrowBuf(unsigned f) : flags(f) {}
+  GrowBuf(const GrowBuf&) = delete;
+  GrowBuf& operator=(const GrowBuf&) = delete;
+  ~GrowBuf() { release(); }
+  void release() {
+    if (p) (void)(kPinned ? hipHostFree(p) : hipFree(p));
+    p = nullptr;
+    n = 0;
+  }
+  int grow(size_t want) {
+    if (n >= want) return GR_OK;
+    release();
+    if ((kPinned ? hipHostMalloc((void**)&p, want, flags) : hipMalloc((void**)&p, want)) != hipSuccess) {
+      p = nullptr;
+      return GR_EDEVICE;
+    }
+    n = want;
+    return GR_OK;
+  }
+  template <class T>
+  T* as() const {
+    return (T*)p;
+  }
+};
 
 struct gr_engine {
   gr_config cfg{};
@@ -147,11 +186,9 @@ struct gr_engine {
   uint32_t* qraw = nullptr;
   std::string wclock_path;
 
-  // gr_step buffers (gr_io.h), grown on demand and reused
-  struct Buf {
-    void* p = nullptr;
-    size_t n = 0;
-  };
+  // gr_step buffers (gr_io.h)
+  using Buf = GrowBuf<false>;
+  using Pinned = GrowBuf<true>;
   Buf d_in, d_out;          // mailbox spaces
   Buf d_msgs, d_locals;     // caller records, as given
   Buf d_mark, d_lop;        // [max_peers] input flags, lane of peer
@@ -174,24 +211,15 @@ struct gr_engine {
   Buf d_cluster, d_target;
   uint32_t n_targets = 0;
   Buf d_wf, d_wrank, d_wcnt, d_wbase, d_wplan, d_wtot, d_wmsgs, d_wbat, d_wbt;
-  uint8_t* h_wbt = nullptr;   // pinned: batch_target
-  uint8_t* h_wtot = nullptr;  // pinned: message and batch totals
-  size_t h_wbt_bytes = 0, h_wtot_bytes = 0;
-  uint8_t* h_unr = nullptr;  // pinned: unrouted indices + reasons
-  size_t h_unr_bytes = 0;
-  uint8_t* h_inmsgs = nullptr;   // pinned inbox the caller may fill in place (gr_inbox_reserve)
-  uint8_t* h_inlocals = nullptr;
-  size_t h_inmsgs_bytes = 0, h_inlocals_bytes = 0;
-  uint8_t* h_outmsgs = nullptr;  // pinned: returned to the caller until gr_release_outbox
-  uint8_t* h_results = nullptr;
-  uint8_t* h_scal = nullptr;
-  size_t h_outmsgs_bytes = 0, h_results_bytes = 0, h_scal_bytes = 0;
-  uint8_t* h_inext = nullptr;  // gr_cinbox_reserve's ext arrays (the compact ones reuse h_inmsgs / h_inlocals)
-  uint8_t* h_inlext = nullptr;
-  size_t h_inext_bytes = 0, h_inlext_bytes = 0;
-  uint8_t* h_outext = nullptr;  // gr_step_compact's ext outputs (the compact ones reuse h_outmsgs / h_results)
-  uint8_t* h_resext = nullptr;
-  size_t h_outext_bytes = 0, h_resext_bytes = 0;
+  Pinned h_wbt;   // batch_target
+  Pinned h_wtot;  // message and batch totals
+  Pinned h_unr;   // unrouted indices + reasons
+  Pinned h_inmsgs{kInboxPinned}, h_inlocals{kInboxPinned};  // inbox the caller may fill in place (gr_inbox_reserve)
+  Pinned h_outmsgs, h_results;  // returned to the caller until gr_release_outbox
+  Pinned h_scal;
+  // gr_cinbox_reserve's ext arrays (the compact ones reuse h_inmsgs / h_inlocals)
+  Pinned h_inext{kInboxPinned}, h_inlext{kInboxPinned};
+  Pinned h_outext, h_resext;  // gr_step_compact's ext outputs (the compact ones reuse h_outmsgs / h_results)
   std::mutex mu;  // one host-path pass at a time per engine
   // gr_step_compact_begin -> _end: the uploaded pass waiting for its second half
   struct CPending {
@@ -231,11 +259,6 @@ static void free_timings(gr_engine* e) {
 }
 
 namespace {
-
-#ifndef GR_INBOX_WC
-#define GR_INBOX_WC 1
-#endif
-const unsigned kInboxPinned = GR_INBOX_WC ? (hipHostMallocDefault | hipHostMallocWriteCombined) : hipHostMallocDefault;
 
 // GR_PHASES=1: host-side phase times of a boundary pass on stderr (profiling aid).
 struct PhaseClock {
@@ -316,32 +339,92 @@ int ensure_quiesce(gr_engine* e) {
   return GR_OK;
 }
 
-int grow_device(void** p, size_t* have, size_t want) {
-  if (*have >= want) return GR_OK;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  *have = 0;
-  HIPCHK(hipMalloc(p, want));
-  *have = want;
-  return GR_OK;
-}
-// flags: hipHostMallocDefault for what the host reads (outboxes), write-combined
-// for the inboxes the host only writes and the device reads once (no snooping of
-// dirty host cache lines during the upload).
-int grow_pinned(uint8_t** p, size_t* have, size_t want, unsigned flags = hipHostMallocDefault) {
-  if (*have >= want) return GR_OK;
-  if (*p) (void)hipHostFree(*p);
-  *p = nullptr;
-  *have = 0;
-  HIPCHK(hipHostMalloc((void**)p, want, flags));
-  *have = want;
-  return GR_OK;
+// d_scal / h_scal: the four words a pass's counts, totals and error flags come down in.
+int ensure_scal(gr_engine* e) {
+  const int r = e->d_scal.grow(16);
+  return r ? r : e->h_scal.grow(16);
 }
 
 // Grid of a boundary pass (grid-stride loops): enough workgroups to fill the chip.
 uint32_t io_grid(size_t n) {
   const size_t b = (n + io::kIoBlock - 1) / io::kIoBlock;
   return (uint32_t)std::max<size_t>(1, std::min<size_t>(b, 4096));
+}
+
+// A slot list into e->d_slots, on e->stream.
+int upload_slots(gr_engine* e, const uint32_t* slots, size_t n, const uint32_t** d_slots) {
+  const int r = e->d_slots.grow(n * 4);
+  if (r) return r;
+  HIPCHK(hipMemcpyAsync(e->d_slots.p, slots, n * 4, hipMemcpyHostToDevice, e->stream));
+  *d_slots = e->d_slots.as<const uint32_t>();
+  return GR_OK;
+}
+
+// The operations over a slot list and one record per listed slot (gpuraft.h):
+// their checks and refusals, in the one order all of them document, around the
+// kernel `launch` enqueues.
+//  1. a null engine, or null slots / records with n != 0: GR_EINVAL
+//  2. n == 0: GR_OK
+//  3. n >= 2^31: GR_EINVAL
+//  4. a slot out of range or listed twice: GR_ERANGE (nothing written)
+//  5. the engine's lock
+//  6. a pending gr_step_compact_begin: GR_ESTATE
+//  7. a record `known` does not take: GR_EINVAL
+//  8. hipDeviceSynchronize (passes in flight on other streams own the rows and side arrays)
+//  9. the slots, and with SL_UP the records, into d_slots / d_peers
+// With SL_STATUS a status per record follows the records in d_peers and comes
+// down into `status` (when given), the kernel raises `refused` for any status
+// but 0, and the call is then GR_ESTATE. With SL_DOWN the records come down.
+enum : unsigned { SL_UP = 1, SL_DOWN = 2, SL_STATUS = 4 };
+template <class Rec>
+struct SlotArgs {
+  dim3 grid, blk;
+  hipStream_t s;
+  const uint32_t* slots;  // device
+  Rec* recs;              // device
+  uint32_t n;
+  int32_t* status;    // device (SL_STATUS)
+  uint32_t* refused;  // device (SL_STATUS)
+};
+template <class Rec, class Launch>
+int slot_list_op(gr_engine* e, const uint32_t* slots, Rec* recs, size_t n, unsigned mode, int32_t* status,
+                 Launch launch, bool (*known)(const Rec&) = nullptr) {
+  if (!e || (n && (!slots || !recs))) return GR_EINVAL;
+  if (n == 0) return GR_OK;
+  if (n >= 0x80000000ull) return GR_EINVAL;
+  const uint32_t cap = e->cfg.max_peers;
+  std::vector<uint64_t> seen((cap + 63) / 64, 0);
+  for (size_t x = 0; x < n; ++x) {
+    const uint32_t p = slots[x];
+    if (p >= cap || (seen[p >> 6] >> (p & 63)) & 1) return GR_ERANGE;  // nothing written
+    seen[p >> 6] |= 1ull << (p & 63);
+  }
+  std::lock_guard<std::mutex> guard(e->mu);
+  GR_REFUSE_PENDING(e);
+  for (size_t x = 0; known && x < n; ++x)
+    if (!known(recs[x])) return GR_EINVAL;
+  HIPCHK(hipDeviceSynchronize());
+  const bool st = mode & SL_STATUS;
+  const size_t bytes = n * sizeof(Rec);
+  SlotArgs<Rec> a{dim3(io_grid(n)), dim3(io::kIoBlock), e->stream, nullptr, nullptr, (uint32_t)n, nullptr, nullptr};
+  int r;
+  if ((r = upload_slots(e, slots, n, &a.slots))) return r;
+  if ((r = e->d_peers.grow(st ? bytes + n * 4 + 16 : bytes))) return r;
+  a.recs = e->d_peers.as<Rec>();
+  if (mode & SL_UP) HIPCHK(hipMemcpyAsync((void*)a.recs, recs, bytes, hipMemcpyHostToDevice, a.s));
+  if (st) {
+    if ((r = ensure_scal(e))) return r;
+    a.status = (int32_t*)(a.recs + n);
+    a.refused = e->d_scal.as<uint32_t>();
+    HIPCHK(hipMemsetAsync(a.refused, 0, 16, a.s));
+  }
+  if ((r = launch(a))) return r;
+  HIPCHK(hipGetLastError());
+  if (mode & SL_DOWN) HIPCHK(hipMemcpyAsync((void*)recs, a.recs, bytes, hipMemcpyDeviceToHost, a.s));
+  if (st && status) HIPCHK(hipMemcpyAsync(status, a.status, n * 4, hipMemcpyDeviceToHost, a.s));
+  if (st) HIPCHK(hipMemcpyAsync(e->h_scal.p, a.refused, 4, hipMemcpyDeviceToHost, a.s));
+  HIPCHK(hipStreamSynchronize(a.s));
+  return st && *e->h_scal.as<uint32_t>() ? GR_ESTATE : GR_OK;
 }
 
 // gr_peer records <-> state rows for slots [first, first+n) or a slot list
@@ -361,28 +444,23 @@ int transfer(gr_engine* e, const uint32_t* slots, uint32_t first, size_t n, gr_p
   const hipStream_t s = e->stream;
   const size_t bytes = n * sizeof(gr_peer);
   int r;
-  if ((r = grow_device(&e->d_peers.p, &e->d_peers.n, bytes))) return r;
+  if ((r = e->d_peers.grow(bytes))) return r;
   const uint32_t* dslots = nullptr;
-  if (slots) {
-    if ((r = grow_device(&e->d_slots.p, &e->d_slots.n, n * 4))) return r;
-    HIPCHK(hipMemcpyAsync(e->d_slots.p, slots, n * 4, hipMemcpyHostToDevice, s));
-    dslots = (const uint32_t*)e->d_slots.p;
-  }
+  if (slots && (r = upload_slots(e, slots, n, &dslots))) return r;
   gr_peer* dp = (gr_peer*)e->d_peers.p;
   const dim3 grid(io_grid(n)), blk(io::kIoBlock);
   if (to_device) {
-    if ((r = grow_device(&e->d_mark.p, &e->d_mark.n, (size_t)cap * 4))) return r;
-    if ((r = grow_device(&e->d_scal.p, &e->d_scal.n, 16))) return r;
-    if ((r = grow_pinned(&e->h_scal, &e->h_scal_bytes, 16))) return r;
+    if ((r = e->d_mark.grow((size_t)cap * 4))) return r;
+    if ((r = ensure_scal(e))) return r;
     HIPCHK(hipMemcpyAsync(dp, host, bytes, hipMemcpyHostToDevice, s));
     if (slots) HIPCHK(hipMemsetAsync(e->d_mark.p, 0, (size_t)cap * 4, s));
     HIPCHK(hipMemsetAsync(e->d_scal.p, 0, 16, s));
     hipLaunchKernelGGL(io::check_peers, grid, blk, 0, s, (const gr_peer*)dp, dslots, (uint32_t)n, e->S, cap,
                        (uint32_t*)e->d_mark.p, (uint32_t*)e->d_scal.p);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(e->h_scal, e->d_scal.p, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(e->h_scal.p, e->d_scal.p, 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    const uint32_t err = *(uint32_t*)e->h_scal;
+    const uint32_t err = *(uint32_t*)e->h_scal.p;
     if (err & io::ERR_SLOT) return GR_ERANGE;  // no row was written
     if (err & io::ERR_PEER) return GR_EINVAL;
     hipLaunchKernelGGL(io::peers_to_rows, grid, blk, 0, s, (const gr_peer*)dp, dslots, first, (uint32_t)n, e->st,
@@ -402,7 +480,7 @@ int transfer(gr_engine* e, const uint32_t* slots, uint32_t first, size_t n, gr_p
 template <class T>
 int io_scan_t(gr_engine* e, const T* in, T* out, uint32_t n, hipStream_t s) {
   if (n == 0) return GR_OK;
-  const int r = grow_device(&e->d_tmp.p, &e->d_tmp.n, (size_t)scan::scan_tiles_of(n) * sizeof(T));
+  const int r = e->d_tmp.grow((size_t)scan::scan_tiles_of(n) * sizeof(T));
   if (r) return r;
   HIPCHK(scan::exclusive_scan<T>(in, out, n, (T*)e->d_tmp.p, s));
   return GR_OK;
@@ -420,8 +498,8 @@ int io_scan64(gr_engine* e, const uint64_t* in, uint64_t* out, uint32_t n, hipSt
 // d_skeys/d_sidx. d_idx holds each record's slot in its mailbox meanwhile.
 int sort_keys(gr_engine* e, uint32_t nm, uint32_t positions, hipStream_t s) {
   int r;
-  if ((r = grow_device(&e->d_kcnt.p, &e->d_kcnt.n, (size_t)positions * 4 + 4))) return r;
-  if ((r = grow_device(&e->d_kbase.p, &e->d_kbase.n, (size_t)positions * 4 + 4))) return r;
+  if ((r = e->d_kcnt.grow((size_t)positions * 4 + 4))) return r;
+  if ((r = e->d_kbase.grow((size_t)positions * 4 + 4))) return r;
   uint32_t* cnt = (uint32_t*)e->d_kcnt.p;
   uint32_t* base = (uint32_t*)e->d_kbase.p;
   HIPCHK(hipMemsetAsync(cnt, 0, (size_t)positions * 4, s));
@@ -437,6 +515,167 @@ int sort_keys(gr_engine* e, uint32_t nm, uint32_t positions, hipStream_t s) {
   hipLaunchKernelGGL(io::key_order, dim3(io_grid(positions)), blk, 0, s, (const uint32_t*)cnt,
                      (const uint32_t*)base, positions, (uint32_t*)e->d_sidx.p);
   HIPCHK(hipGetLastError());
+  return GR_OK;
+}
+
+// ---------------------------------------------------------------- the staged host pass
+// gr_step, the wire path and gr_step_compact run one sequence of boundary
+// passes (gr_io.h) around the step kernels: inbox records -> lanes
+// (stage_lanes), then mailboxes, lane rows and the pass itself
+// (run_staged_pass), then the outbox. The inbox, already in HBM, is full
+// records (FullInbox) or compact ones (CompactInbox): each names the kernels
+// that read its record type; nothing else differs.
+struct FullInbox {
+  const gr_message* msgs;
+  uint32_t n_msgs;
+  const gr_local_input* loc;
+  uint32_t n_loc;
+  uint32_t n_tick_recs() const { return n_loc; }
+  void check_raw_ticks(dim3 g, hipStream_t s, uint32_t* err) const {
+    hipLaunchKernelGGL(io::check_raw_ticks, g, dim3(io::kIoBlock), 0, s, loc, n_loc, err);
+  }
+  void mark(dim3 g, hipStream_t s, uint32_t S, uint32_t cap, uint32_t* mark, uint32_t* err, uint32_t ce) const {
+    hipLaunchKernelGGL(io::mark_inputs, g, dim3(io::kIoBlock), 0, s, msgs, n_msgs, loc, n_loc, S, cap, mark, err, ce);
+  }
+  void keys(dim3 g, hipStream_t s, const uint32_t* lop, uint32_t nl, uint32_t* keys, uint32_t* idx) const {
+    hipLaunchKernelGGL(io::msg_keys, g, dim3(io::kIoBlock), 0, s, msgs, n_msgs, lop, nl, keys, idx);
+  }
+  void encode(dim3 g, hipStream_t s, const uint32_t* skeys, const uint32_t* sidx, const SpaceView& vin,
+              uint32_t ce) const {
+    hipLaunchKernelGGL(io::encode_sorted, g, dim3(io::kIoBlock), 0, s, msgs, skeys, sidx, n_msgs, vin, ce);
+  }
+  void winner(dim3 g, hipStream_t s, const uint32_t* lop, uint32_t* win) const {
+    hipLaunchKernelGGL(io::local_winner, g, dim3(io::kIoBlock), 0, s, loc, n_loc, lop, win);
+  }
+  void fill(dim3 g, hipStream_t s, const uint32_t* win, uint32_t nl, const LaneBase& ln) const {
+    hipLaunchKernelGGL(io::fill_locals, g, dim3(io::kIoBlock), 0, s, loc, win, nl, ln);
+  }
+};
+
+struct CompactInbox {
+  io::CInbox ci;
+  uint32_t n_msgs, n_loc;  // ci.n_msgs, ci.n_loc
+  // the engine's compact inbox buffers, holding these many records
+  CompactInbox(gr_engine* e, uint32_t nm, uint32_t nlc, uint32_t nx, uint32_t nlx) : n_msgs(nm), n_loc(nlc) {
+    ci.msgs = e->d_msgs.as<const gr_cmsg>();
+    ci.ext = e->d_ext.as<const gr_message>();
+    ci.loc = e->d_locals.as<const gr_clocal>();
+    ci.lext = e->d_lext.as<const gr_local_input>();
+    ci.n_msgs = nm;
+    ci.n_ext = nx;
+    ci.n_loc = nlc;
+    ci.n_lext = nlx;
+  }
+  uint32_t n_tick_recs() const { return ci.n_loc + ci.n_lext; }
+  void check_raw_ticks(dim3 g, hipStream_t s, uint32_t* err) const {
+    hipLaunchKernelGGL(io::check_raw_ticks_c, g, dim3(io::kIoBlock), 0, s, ci.loc, ci.n_loc, ci.lext, ci.n_lext, err);
+  }
+  void mark(dim3 g, hipStream_t s, uint32_t S, uint32_t cap, uint32_t* mark, uint32_t* err, uint32_t ce) const {
+    hipLaunchKernelGGL(io::mark_inputs_c, g, dim3(io::kIoBlock), 0, s, ci, S, cap, mark, err, ce);
+  }
+  void keys(dim3 g, hipStream_t s, const uint32_t* lop, uint32_t nl, uint32_t* keys, uint32_t* idx) const {
+    hipLaunchKernelGGL(io::msg_keys_c, g, dim3(io::kIoBlock), 0, s, ci.msgs, ci.n_msgs, lop, nl, keys, idx);
+  }
+  void encode(dim3 g, hipStream_t s, const uint32_t* skeys, const uint32_t* sidx, const SpaceView& vin,
+              uint32_t ce) const {
+    hipLaunchKernelGGL(io::encode_sorted_c, g, dim3(io::kIoBlock), 0, s, ci, skeys, sidx, vin, ce);
+  }
+  void winner(dim3 g, hipStream_t s, const uint32_t* lop, uint32_t* win) const {
+    hipLaunchKernelGGL(io::local_winner_c, g, dim3(io::kIoBlock), 0, s, ci.loc, ci.n_loc, lop, win);
+  }
+  void fill(dim3 g, hipStream_t s, const uint32_t* win, uint32_t nl, const LaneBase& ln) const {
+    hipLaunchKernelGGL(io::fill_locals_c, g, dim3(io::kIoBlock), 0, s, ci, win, nl, ln);
+  }
+};
+
+// Inbox records -> lanes: every slot with input marked (d_mark) and numbered
+// (d_lop); waits for the lane count. *err: some record is refused (a slot out of
+// range, a QuiescedTick count with the quiesce manager on the device): nothing
+// of the pass may run. Caller holds e->mu.
+template <class In>
+int stage_lanes(gr_engine* e, const In& in, uint32_t* nl, uint32_t* err) {
+  const uint32_t S = e->S, cap = e->cfg.max_peers;
+  const hipStream_t s = e->stream;
+  int r;
+  if ((r = e->d_mark.grow((size_t)cap * 4))) return r;
+  if ((r = e->d_lop.grow((size_t)cap * 4))) return r;
+  if ((r = ensure_scal(e))) return r;
+  uint32_t* mark = e->d_mark.as<uint32_t>();
+  uint32_t* lop = e->d_lop.as<uint32_t>();
+  uint32_t* scal = e->d_scal.as<uint32_t>();
+  HIPCHK(hipMemsetAsync(mark, 0, (size_t)cap * 4, s));
+  HIPCHK(hipMemsetAsync(scal, 0, 16, s));
+  if (e->quiesce && in.n_tick_recs()) {  // ticks are LocalTicks: a QuiescedTick count is refused (scal[1])
+    in.check_raw_ticks(dim3(io_grid(in.n_tick_recs())), s, scal + 1);
+    HIPCHK(hipGetLastError());
+  }
+  in.mark(dim3(io_grid(in.n_msgs + in.n_loc)), s, S, cap, mark, scal + 1, (uint32_t)e->config_entries);
+  HIPCHK(hipGetLastError());
+  if ((r = io_scan(e, mark, lop, cap, s))) return r;
+  hipLaunchKernelGGL(io::finish_lanes, dim3(1), dim3(64), 0, s, (const uint32_t*)mark, (const uint32_t*)lop, cap,
+                     (const uint32_t*)(scal + 1), scal);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(e->h_scal.p, scal, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  *nl = e->h_scal.as<uint32_t>()[0];
+  *err = e->h_scal.as<uint32_t>()[1];
+  return GR_OK;
+}
+
+// The nl > 0 lanes stage_lanes numbered: their mailboxes (slot-major j*nl +
+// lane, arrival order kept by a stable sort), their lane rows, and the pass,
+// enqueued on e->stream; *vout is the space it writes. Caller holds e->mu.
+template <class In>
+int run_staged_pass(gr_engine* e, const In& in, uint32_t nl, SpaceView* vout) {
+  const uint32_t S = e->S, cap = e->cfg.max_peers, nm = in.n_msgs, nlc = in.n_loc;
+  const hipStream_t s = e->stream;
+  const dim3 blk(io::kIoBlock);
+  int r;
+  const uint32_t* mark = e->d_mark.as<const uint32_t>();
+  const uint32_t* lop = e->d_lop.as<const uint32_t>();
+  hipLaunchKernelGGL(io::lane_peers, dim3(io_grid(cap)), blk, 0, s, mark, lop, cap, e->ln.u32(LR_LANE_PEER));
+  HIPCHK(hipGetLastError());
+  // ---- mailboxes
+  const uint32_t positions = nl * S;
+  const size_t space = gr_space_bytes(1, positions, GR_C);
+  if ((r = e->d_in.grow(space))) return r;
+  if ((r = e->d_out.grow(space))) return r;
+  const SpaceView vin = make_view(e->d_in.p, 1, positions);
+  *vout = make_view(e->d_out.p, 1, positions);
+  hipLaunchKernelGGL(io::clear_counts, dim3(io_grid(vin.pc)), blk, 0, s, vin, vin.pc);  // the count bytes
+  HIPCHK(hipGetLastError());
+  if (nm) {
+    for (gr_engine::Buf* b : {&e->d_keys, &e->d_idx, &e->d_skeys, &e->d_sidx})
+      if ((r = b->grow((size_t)nm * 4))) return r;
+    in.keys(dim3(io_grid(nm)), s, lop, nl, e->d_keys.as<uint32_t>(), e->d_idx.as<uint32_t>());
+    HIPCHK(hipGetLastError());
+    if ((r = sort_keys(e, nm, positions, s))) return r;
+    in.encode(dim3(io_grid(nm)), s, e->d_skeys.as<const uint32_t>(), e->d_sidx.as<const uint32_t>(), vin,
+              (uint32_t)e->config_entries);
+    HIPCHK(hipGetLastError());
+  }
+  // ---- locals -> lane rows
+  if ((r = e->d_win.grow((size_t)nl * 4))) return r;
+  HIPCHK(hipMemsetAsync(e->d_win.p, 0, (size_t)nl * 4, s));
+  if (nlc) {
+    in.winner(dim3(io_grid(nlc)), s, lop, e->d_win.as<uint32_t>());
+    HIPCHK(hipGetLastError());
+  }
+  in.fill(dim3(io_grid(nl)), s, e->d_win.as<const uint32_t>(), nl, e->ln);
+  HIPCHK(hipGetLastError());
+  // ---- the pass
+  StepParams kp = base_params(e);
+  kp.has_locals = 1;
+  kp.has_lane_peer = 1;
+  kp.route_mode = RT_IDENTITY;
+  kp.in = vin;
+  kp.out = *vout;
+  kp.n_lanes = nl;
+  kp.qraw = e->ln.u32(LR_TICKS);  // this pass's rows are the raw input: the quiesce pass rewrites them in place
+  HIPCHK(launch_slots(S, kp, e->bail, e->counters, e->cap, (uint32_t)e->launches++, s, next_timing(e)));
+  e->passes++;
+  e->locals_set = false;    // the lane rows now hold this pass's compact locals
+  e->routes_bound = false;  // and RT_IDENTITY replaced the bound routes
   return GR_OK;
 }
 
@@ -584,19 +823,8 @@ void gr_destroy(gr_engine* e) {
     (void)hipFree(e->wclock);
   }
   free_timings(e);
-  for (gr_engine::Buf* b : {&e->d_in, &e->d_out, &e->d_msgs, &e->d_locals, &e->d_mark, &e->d_lop, &e->d_keys,
-                            &e->d_idx, &e->d_skeys, &e->d_sidx, &e->d_win, &e->d_oc, &e->d_off, &e->d_tmp,
-                            &e->d_scal, &e->d_outmsgs, &e->d_results, &e->d_peers, &e->d_slots, &e->d_ext,
-                            &e->d_lext, &e->d_oc64, &e->d_off64, &e->d_rx, &e->d_roff, &e->d_outext,
-                            &e->d_resext, &e->d_nodes, &e->d_wrec, &e->d_why, &e->d_unr, &e->d_kcnt, &e->d_kbase,
-                            &e->d_cluster, &e->d_target, &e->d_wf, &e->d_wrank, &e->d_wcnt, &e->d_wbase, &e->d_wplan,
-                            &e->d_wtot, &e->d_wmsgs, &e->d_wbat, &e->d_wbt})
-    if (b->p) (void)hipFree(b->p);
-  for (uint8_t* h : {e->h_outmsgs, e->h_results, e->h_scal, e->h_inmsgs, e->h_inlocals, e->h_inext, e->h_inlext,
-                     e->h_outext, e->h_resext, e->h_unr, e->h_wbt, e->h_wtot})
-    if (h) (void)hipHostFree(h);
   if (e->stream) (void)hipStreamDestroy(e->stream);
-  delete e;
+  delete e;  // and its Buf and Pinned members
 }
 
 int gr_load_groups(gr_engine* e, uint32_t first, const gr_peer* peers, size_t n) {
@@ -622,89 +850,23 @@ int gr_sync_peers_to_host(gr_engine* e, const uint32_t* slots, gr_peer* out, siz
 // after compaction term() answers 0 below it and Replicate sends below it take
 // the snapshot path, as in the reference.
 int gr_compact_log(gr_engine* e, const uint32_t* slots, const uint64_t* index, size_t n, int32_t* status) {
-  if (!e || (n && (!slots || !index))) return GR_EINVAL;
-  if (n == 0) return GR_OK;
-  if (n >= 0x80000000ull) return GR_EINVAL;
-  const uint32_t cap = e->cfg.max_peers;
-  std::vector<uint64_t> seen((cap + 63) / 64, 0);
-  for (size_t x = 0; x < n; ++x) {
-    const uint32_t p = slots[x];
-    if (p >= cap || (seen[p >> 6] >> (p & 63)) & 1) return GR_ERANGE;  // nothing written
-    seen[p >> 6] |= 1ull << (p & 63);
-  }
-  std::lock_guard<std::mutex> guard(e->mu);
-  GR_REFUSE_PENDING(e);
-  HIPCHK(hipDeviceSynchronize());  // passes in flight on other streams own the rows
-  const hipStream_t s = e->stream;
-  int r;
-  if ((r = grow_device(&e->d_slots.p, &e->d_slots.n, n * 4))) return r;
-  if ((r = grow_device(&e->d_peers.p, &e->d_peers.n, n * 12 + 16))) return r;
-  if ((r = grow_device(&e->d_scal.p, &e->d_scal.n, 16))) return r;
-  if ((r = grow_pinned(&e->h_scal, &e->h_scal_bytes, 16))) return r;
-  uint64_t* didx = (uint64_t*)e->d_peers.p;
-  int32_t* dst = (int32_t*)(didx + n);
-  HIPCHK(hipMemcpyAsync(e->d_slots.p, slots, n * 4, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(didx, index, n * 8, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemsetAsync(e->d_scal.p, 0, 16, s));
-  const dim3 grid(io_grid(n)), blk(io::kIoBlock);
-  const uint32_t* ds = (const uint32_t*)e->d_slots.p;
-  uint32_t* refused = (uint32_t*)e->d_scal.p;
-  switch (e->S) {
-#define GR_COMPACT_CASE(SS)                                                                                 \
-  case SS:                                                                                                  \
-    hipLaunchKernelGGL(io::compact_rows<SS>, grid, blk, 0, s, e->st, ds, (const uint64_t*)didx, (uint32_t)n, \
-                       dst, refused);                                                                       \
-    break;
-    GR_COMPACT_CASE(1) GR_COMPACT_CASE(2) GR_COMPACT_CASE(3) GR_COMPACT_CASE(4)
-    GR_COMPACT_CASE(5) GR_COMPACT_CASE(6) GR_COMPACT_CASE(7) GR_COMPACT_CASE(8)
-#undef GR_COMPACT_CASE
-    default: return GR_EINVAL;
-  }
-  HIPCHK(hipGetLastError());
-  if (status) HIPCHK(hipMemcpyAsync(status, dst, n * 4, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(e->h_scal, refused, 4, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  return *(uint32_t*)e->h_scal ? GR_ESTATE : GR_OK;
+  return slot_list_op(e, slots, index, n, SL_UP | SL_STATUS, status, [e](const SlotArgs<const uint64_t>& a) {
+    return with_slots(e->S, [&](auto ss) {
+      hipLaunchKernelGGL(io::compact_rows<decltype(ss)::value>, a.grid, a.blk, 0, a.s, e->st, a.slots, a.recs, a.n,
+                         a.status, a.refused);
+      return GR_OK;
+    });
+  });
 }
 
 // entryLog.commitUpdate (logentry.go:325-335) for a slot list: the host's
 // persistence/apply acknowledgement moves inMemory.savedTo / markerIndex and
 // entryLog.applied on the device (gr_io.h commit_rows).
 int gr_commit_update(gr_engine* e, const uint32_t* slots, const gr_update_commit* uc, size_t n, int32_t* status) {
-  if (!e || (n && (!slots || !uc))) return GR_EINVAL;
-  if (n == 0) return GR_OK;
-  if (n >= 0x80000000ull) return GR_EINVAL;
-  const uint32_t cap = e->cfg.max_peers;
-  std::vector<uint64_t> seen((cap + 63) / 64, 0);
-  for (size_t x = 0; x < n; ++x) {
-    const uint32_t p = slots[x];
-    if (p >= cap || (seen[p >> 6] >> (p & 63)) & 1) return GR_ERANGE;  // nothing written
-    seen[p >> 6] |= 1ull << (p & 63);
-  }
-  std::lock_guard<std::mutex> guard(e->mu);
-  GR_REFUSE_PENDING(e);
-  HIPCHK(hipDeviceSynchronize());  // passes in flight on other streams own the rows
-  const hipStream_t s = e->stream;
-  int r;
-  if ((r = grow_device(&e->d_slots.p, &e->d_slots.n, n * 4))) return r;
-  if ((r = grow_device(&e->d_peers.p, &e->d_peers.n, n * (sizeof(gr_update_commit) + 4) + 16))) return r;
-  if ((r = grow_device(&e->d_scal.p, &e->d_scal.n, 16))) return r;
-  if ((r = grow_pinned(&e->h_scal, &e->h_scal_bytes, 16))) return r;
-  gr_update_commit* duc = (gr_update_commit*)e->d_peers.p;
-  int32_t* dst = (int32_t*)(duc + n);
-  HIPCHK(hipMemcpyAsync(e->d_slots.p, slots, n * 4, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(duc, uc, n * sizeof(gr_update_commit), hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemsetAsync(e->d_scal.p, 0, 16, s));
-  const dim3 grid(io_grid(n)), blk(io::kIoBlock);
-  const uint32_t* ds = (const uint32_t*)e->d_slots.p;
-  uint32_t* refused = (uint32_t*)e->d_scal.p;
-  hipLaunchKernelGGL(io::commit_rows, grid, blk, 0, s, e->st, ds, (const gr_update_commit*)duc, (uint32_t)n, dst,
-                     refused);
-  HIPCHK(hipGetLastError());
-  if (status) HIPCHK(hipMemcpyAsync(status, dst, n * 4, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(e->h_scal, refused, 4, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  return *(uint32_t*)e->h_scal ? GR_ESTATE : GR_OK;
+  return slot_list_op(e, slots, uc, n, SL_UP | SL_STATUS, status, [e](const SlotArgs<const gr_update_commit>& a) {
+    hipLaunchKernelGGL(io::commit_rows, a.grid, a.blk, 0, a.s, e->st, a.slots, a.recs, a.n, a.status, a.refused);
+    return GR_OK;
+  });
 }
 
 // Peer.ApplyConfigChange / RejectConfigChange (peer.go:153-174) for a slot list
@@ -712,219 +874,74 @@ int gr_commit_update(gr_engine* e, const uint32_t* slots, const gr_update_commit
 // the membership itself never leaves the device.
 int gr_apply_config_change(gr_engine* e, const uint32_t* slots, const gr_config_change* cc, size_t n,
                            int32_t* status) {
-  if (!e || (n && (!slots || !cc))) return GR_EINVAL;
-  if (n == 0) return GR_OK;
-  if (n >= 0x80000000ull) return GR_EINVAL;
-  const uint32_t cap = e->cfg.max_peers;
-  std::vector<uint64_t> seen((cap + 63) / 64, 0);
-  for (size_t x = 0; x < n; ++x) {
-    const uint32_t p = slots[x];
-    if (p >= cap || (seen[p >> 6] >> (p & 63)) & 1) return GR_ERANGE;  // nothing written
-    seen[p >> 6] |= 1ull << (p & 63);
-  }
-  std::lock_guard<std::mutex> guard(e->mu);
-  GR_REFUSE_PENDING(e);  // from here on as gr_compact_log, so the same states give the same codes
-  for (size_t x = 0; x < n; ++x)
-    if (!conf::known_type(cc[x].type)) return GR_EINVAL;  // "unexpected config change type", peer.go:166-167
-  HIPCHK(hipDeviceSynchronize());  // passes in flight on other streams own the rows
-  const hipStream_t s = e->stream;
-  int r;
-  if ((r = grow_device(&e->d_slots.p, &e->d_slots.n, n * 4))) return r;
-  if ((r = grow_device(&e->d_peers.p, &e->d_peers.n, n * (sizeof(gr_config_change) + 4) + 16))) return r;
-  if ((r = grow_device(&e->d_scal.p, &e->d_scal.n, 16))) return r;
-  if ((r = grow_pinned(&e->h_scal, &e->h_scal_bytes, 16))) return r;
-  gr_config_change* dcc = (gr_config_change*)e->d_peers.p;
-  int32_t* dst = (int32_t*)(dcc + n);
-  HIPCHK(hipMemcpyAsync(e->d_slots.p, slots, n * 4, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(dcc, cc, n * sizeof(gr_config_change), hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemsetAsync(e->d_scal.p, 0, 16, s));
-  const dim3 grid(io_grid(n)), blk(io::kIoBlock);
-  const uint32_t* ds = (const uint32_t*)e->d_slots.p;
-  uint32_t* refused = (uint32_t*)e->d_scal.p;
-  switch (e->S) {  // the instantiated slot counts (instantiated_slots)
-#define GR_CONFIG_CASE(SS)                                                                                         \
-  case SS:                                                                                                         \
-    hipLaunchKernelGGL(io::config_rows<SS>, grid, blk, 0, s, e->st, ds, (const gr_config_change*)dcc, (uint32_t)n, \
-                       dst, refused);                                                                              \
-    break;
-    GR_CONFIG_CASE(1) GR_CONFIG_CASE(3) GR_CONFIG_CASE(5) GR_CONFIG_CASE(8)
-#undef GR_CONFIG_CASE
-    default: return GR_EINVAL;
-  }
-  HIPCHK(hipGetLastError());
-  if (status) HIPCHK(hipMemcpyAsync(status, dst, n * 4, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(e->h_scal, refused, 4, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  return *(uint32_t*)e->h_scal ? GR_ESTATE : GR_OK;
+  return slot_list_op<const gr_config_change>(
+      e, slots, cc, n, SL_UP | SL_STATUS, status,
+      [e](const SlotArgs<const gr_config_change>& a) {
+        return with_slots(e->S, [&](auto ss) {
+          hipLaunchKernelGGL(io::config_rows<decltype(ss)::value>, a.grid, a.blk, 0, a.s, e->st, a.slots, a.recs, a.n,
+                             a.status, a.refused);
+          return GR_OK;
+        });
+      },
+      // "unexpected config change type", peer.go:166-167
+      [](const gr_config_change& c) { return conf::known_type(c.type); });
 }
 
 // Peer.RestoreRemotes (peer.go:177-180) for a slot list (gr_config_change.h
 // restore_rows, gr_io.h restore_remote_rows): the 80-byte membership and the
-// slot go up, a status comes down. Checks and refusals in gr_apply_config_change's order.
+// slot go up, a status comes down.
 int gr_restore_remotes(gr_engine* e, const uint32_t* slots, const gr_membership* ms, size_t n, int32_t* status) {
-  if (!e || (n && (!slots || !ms))) return GR_EINVAL;
-  if (n == 0) return GR_OK;
-  if (n >= 0x80000000ull) return GR_EINVAL;
-  const uint32_t cap = e->cfg.max_peers;
-  std::vector<uint64_t> seen((cap + 63) / 64, 0);
-  for (size_t x = 0; x < n; ++x) {
-    const uint32_t p = slots[x];
-    if (p >= cap || (seen[p >> 6] >> (p & 63)) & 1) return GR_ERANGE;  // nothing written
-    seen[p >> 6] |= 1ull << (p & 63);
-  }
-  std::lock_guard<std::mutex> guard(e->mu);
-  GR_REFUSE_PENDING(e);
-  for (size_t x = 0; x < n; ++x)
-    if (!conf::known_kinds(ms[x])) return GR_EINVAL;
-  HIPCHK(hipDeviceSynchronize());  // passes in flight on other streams own the rows
-  const hipStream_t s = e->stream;
-  int r;
-  if ((r = grow_device(&e->d_slots.p, &e->d_slots.n, n * 4))) return r;
-  if ((r = grow_device(&e->d_peers.p, &e->d_peers.n, n * (sizeof(gr_membership) + 4) + 16))) return r;
-  if ((r = grow_device(&e->d_scal.p, &e->d_scal.n, 16))) return r;
-  if ((r = grow_pinned(&e->h_scal, &e->h_scal_bytes, 16))) return r;
-  gr_membership* dms = (gr_membership*)e->d_peers.p;
-  int32_t* dst = (int32_t*)(dms + n);
-  HIPCHK(hipMemcpyAsync(e->d_slots.p, slots, n * 4, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(dms, ms, n * sizeof(gr_membership), hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemsetAsync(e->d_scal.p, 0, 16, s));
-  const dim3 grid(io_grid(n)), blk(io::kIoBlock);
-  const uint32_t* ds = (const uint32_t*)e->d_slots.p;
-  uint32_t* refused = (uint32_t*)e->d_scal.p;
-  switch (e->S) {  // the instantiated slot counts (instantiated_slots)
-#define GR_RESTORE_CASE(SS)                                                                                     \
-  case SS:                                                                                                      \
-    hipLaunchKernelGGL(io::restore_remote_rows<SS>, grid, blk, 0, s, e->st, ds, (const gr_membership*)dms,      \
-                       (uint32_t)n, dst, refused);                                                              \
-    break;
-    GR_RESTORE_CASE(1) GR_RESTORE_CASE(3) GR_RESTORE_CASE(5) GR_RESTORE_CASE(8)
-#undef GR_RESTORE_CASE
-    default: return GR_EINVAL;
-  }
-  HIPCHK(hipGetLastError());
-  if (status) HIPCHK(hipMemcpyAsync(status, dst, n * 4, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(e->h_scal, refused, 4, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  return *(uint32_t*)e->h_scal ? GR_ESTATE : GR_OK;
+  return slot_list_op<const gr_membership>(
+      e, slots, ms, n, SL_UP | SL_STATUS, status,
+      [e](const SlotArgs<const gr_membership>& a) {
+        return with_slots(e->S, [&](auto ss) {
+          hipLaunchKernelGGL(io::restore_remote_rows<decltype(ss)::value>, a.grid, a.blk, 0, a.s, e->st, a.slots,
+                             a.recs, a.n, a.status, a.refused);
+          return GR_OK;
+        });
+      },
+      [](const gr_membership& m) { return conf::known_kinds(m); });
 }
 
 // The snapshot records of a slot list (gpuraft.h): a side array, no state row.
-static int transfer_snapshot_recs(gr_engine* e, const uint32_t* slots, gr_snapshot_rec* host, size_t n, bool to_device) {
-  if (!e || (n && (!slots || !host))) return GR_EINVAL;
-  if (n == 0) return GR_OK;
-  if (n >= 0x80000000ull) return GR_EINVAL;
-  const uint32_t cap = e->cfg.max_peers;
-  std::vector<uint64_t> seen((cap + 63) / 64, 0);
-  for (size_t x = 0; x < n; ++x) {
-    const uint32_t p = slots[x];
-    if (p >= cap || (seen[p >> 6] >> (p & 63)) & 1) return GR_ERANGE;  // nothing written
-    seen[p >> 6] |= 1ull << (p & 63);
-  }
-  std::lock_guard<std::mutex> guard(e->mu);
-  GR_REFUSE_PENDING(e);
-  HIPCHK(hipDeviceSynchronize());  // passes in flight on other streams read and write the records
-  const hipStream_t s = e->stream;
-  const size_t bytes = n * sizeof(gr_snapshot_rec);
-  int r;
-  if ((r = grow_device(&e->d_slots.p, &e->d_slots.n, n * 4))) return r;
-  if ((r = grow_device(&e->d_peers.p, &e->d_peers.n, bytes))) return r;
-  gr_snapshot_rec* d = (gr_snapshot_rec*)e->d_peers.p;
-  HIPCHK(hipMemcpyAsync(e->d_slots.p, slots, n * 4, hipMemcpyHostToDevice, s));
-  const dim3 grid(io_grid(n)), blk(io::kIoBlock);
-  if (to_device) {
-    HIPCHK(hipMemcpyAsync(d, host, bytes, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(io::set_snapshot_recs, grid, blk, 0, s, e->snap_rec, (const uint32_t*)e->d_slots.p,
-                       (const gr_snapshot_rec*)d, (uint32_t)n);
-    HIPCHK(hipGetLastError());
-  } else {
-    hipLaunchKernelGGL(io::get_snapshot_recs, grid, blk, 0, s, (const gr_snapshot_rec*)e->snap_rec,
-                       (const uint32_t*)e->d_slots.p, d, (uint32_t)n);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(host, d, bytes, hipMemcpyDeviceToHost, s));
-  }
-  HIPCHK(hipStreamSynchronize(s));
-  return GR_OK;
-}
 int gr_set_snapshot_recs(gr_engine* e, const uint32_t* slots, const gr_snapshot_rec* recs, size_t n) {
-  return transfer_snapshot_recs(e, slots, const_cast<gr_snapshot_rec*>(recs), n, true);
+  return slot_list_op(e, slots, recs, n, SL_UP, nullptr, [e](const SlotArgs<const gr_snapshot_rec>& a) {
+    hipLaunchKernelGGL(io::set_snapshot_recs, a.grid, a.blk, 0, a.s, e->snap_rec, a.slots, a.recs, a.n);
+    return GR_OK;
+  });
 }
 int gr_get_snapshot_recs(gr_engine* e, const uint32_t* slots, gr_snapshot_rec* out, size_t n) {
-  return transfer_snapshot_recs(e, slots, out, n, false);
+  return slot_list_op(e, slots, out, n, SL_DOWN, nullptr, [e](const SlotArgs<gr_snapshot_rec>& a) {
+    hipLaunchKernelGGL(io::get_snapshot_recs, a.grid, a.blk, 0, a.s, (const gr_snapshot_rec*)e->snap_rec, a.slots,
+                       a.recs, a.n);
+    return GR_OK;
+  });
 }
 
 // The config-change index records of a slot list (gpuraft.h): a side array, as
 // the snapshot records.
-static int transfer_cc_indexes(gr_engine* e, const uint32_t* slots, gr_cc_index* host, size_t n, bool to_device) {
-  if (!e || (n && (!slots || !host))) return GR_EINVAL;
-  if (n == 0) return GR_OK;
-  if (n >= 0x80000000ull) return GR_EINVAL;
-  const uint32_t cap = e->cfg.max_peers;
-  std::vector<uint64_t> seen((cap + 63) / 64, 0);
-  for (size_t x = 0; x < n; ++x) {
-    const uint32_t p = slots[x];
-    if (p >= cap || (seen[p >> 6] >> (p & 63)) & 1) return GR_ERANGE;  // nothing written
-    seen[p >> 6] |= 1ull << (p & 63);
-  }
-  std::lock_guard<std::mutex> guard(e->mu);
-  GR_REFUSE_PENDING(e);
-  HIPCHK(hipDeviceSynchronize());  // passes in flight on other streams read and write the records
-  const hipStream_t s = e->stream;
-  const size_t bytes = n * sizeof(gr_cc_index);
-  int r;
-  if ((r = grow_device(&e->d_slots.p, &e->d_slots.n, n * 4))) return r;
-  if ((r = grow_device(&e->d_peers.p, &e->d_peers.n, bytes))) return r;
-  gr_cc_index* d = (gr_cc_index*)e->d_peers.p;
-  HIPCHK(hipMemcpyAsync(e->d_slots.p, slots, n * 4, hipMemcpyHostToDevice, s));
-  const dim3 grid(io_grid(n)), blk(io::kIoBlock);
-  if (to_device) {
-    HIPCHK(hipMemcpyAsync(d, host, bytes, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(io::set_cc_indexes, grid, blk, 0, s, e->cc_rec, (const uint32_t*)e->d_slots.p,
-                       (const gr_cc_index*)d, (uint32_t)n);
-    HIPCHK(hipGetLastError());
-  } else {
-    hipLaunchKernelGGL(io::get_cc_indexes, grid, blk, 0, s, (const gr_cc_index*)e->cc_rec,
-                       (const uint32_t*)e->d_slots.p, d, (uint32_t)n);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(host, d, bytes, hipMemcpyDeviceToHost, s));
-  }
-  HIPCHK(hipStreamSynchronize(s));
-  return GR_OK;
-}
 int gr_set_cc_indexes(gr_engine* e, const uint32_t* slots, const gr_cc_index* recs, size_t n) {
-  return transfer_cc_indexes(e, slots, const_cast<gr_cc_index*>(recs), n, true);
+  return slot_list_op(e, slots, recs, n, SL_UP, nullptr, [e](const SlotArgs<const gr_cc_index>& a) {
+    hipLaunchKernelGGL(io::set_cc_indexes, a.grid, a.blk, 0, a.s, e->cc_rec, a.slots, a.recs, a.n);
+    return GR_OK;
+  });
 }
 int gr_get_cc_indexes(gr_engine* e, const uint32_t* slots, gr_cc_index* out, size_t n) {
-  return transfer_cc_indexes(e, slots, out, n, false);
+  return slot_list_op(e, slots, out, n, SL_DOWN, nullptr, [e](const SlotArgs<gr_cc_index>& a) {
+    hipLaunchKernelGGL(io::get_cc_indexes, a.grid, a.blk, 0, a.s, (const gr_cc_index*)e->cc_rec, a.slots, a.recs,
+                       a.n);
+    return GR_OK;
+  });
 }
 
 // Peer.NotifyRaftLastApplied (peer.go:282-284) for a slot list: raft.applied =
 // the RSM's batched last applied index, as node.handleEvents does first in
 // every step (node.go:632-635,653). No other field changes.
 int gr_notify_applied(gr_engine* e, const uint32_t* slots, const uint64_t* applied, size_t n) {
-  if (!e || (n && (!slots || !applied))) return GR_EINVAL;
-  if (n == 0) return GR_OK;
-  if (n >= 0x80000000ull) return GR_EINVAL;
-  const uint32_t cap = e->cfg.max_peers;
-  std::vector<uint64_t> seen((cap + 63) / 64, 0);
-  for (size_t x = 0; x < n; ++x) {
-    const uint32_t p = slots[x];
-    if (p >= cap || (seen[p >> 6] >> (p & 63)) & 1) return GR_ERANGE;  // nothing written
-    seen[p >> 6] |= 1ull << (p & 63);
-  }
-  std::lock_guard<std::mutex> guard(e->mu);
-  GR_REFUSE_PENDING(e);
-  HIPCHK(hipDeviceSynchronize());  // passes in flight on other streams own the rows
-  const hipStream_t s = e->stream;
-  int r;
-  if ((r = grow_device(&e->d_slots.p, &e->d_slots.n, n * 4))) return r;
-  if ((r = grow_device(&e->d_peers.p, &e->d_peers.n, n * 8))) return r;
-  HIPCHK(hipMemcpyAsync(e->d_slots.p, slots, n * 4, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(e->d_peers.p, applied, n * 8, hipMemcpyHostToDevice, s));
-  hipLaunchKernelGGL(io::set_row_u64, dim3(io_grid(n)), dim3(io::kIoBlock), 0, s, e->st, (uint32_t)SR_APPLIED,
-                     (const uint32_t*)e->d_slots.p, (const uint64_t*)e->d_peers.p, (uint32_t)n);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(s));
-  return GR_OK;
+  return slot_list_op(e, slots, applied, n, SL_UP, nullptr, [e](const SlotArgs<const uint64_t>& a) {
+    hipLaunchKernelGGL(io::set_row_u64, a.grid, a.blk, 0, a.s, e->st, (uint32_t)SR_APPLIED, a.slots, a.recs, a.n);
+    return GR_OK;
+  });
 }
 
 uint64_t gr_space_chunk_bytes(uint32_t positions, uint32_t depth) {
@@ -950,17 +967,16 @@ int gr_space_cold_used(gr_engine* e, const void* space, uint32_t n_chunks, uint3
   std::lock_guard<std::mutex> guard(e->mu);
   GR_REFUSE_PENDING(e);
   int r;
-  if ((r = grow_device(&e->d_scal.p, &e->d_scal.n, 16))) return r;
-  if ((r = grow_pinned(&e->h_scal, &e->h_scal_bytes, 16))) return r;
+  if ((r = ensure_scal(e))) return r;
   const hipStream_t s = (hipStream_t)stream;
   const SpaceView v = make_view(space, n_chunks, positions, depth);
   uint32_t* flag = (uint32_t*)e->d_scal.p + 3;
   HIPCHK(hipMemsetAsync(flag, 0, 4, s));
   hipLaunchKernelGGL(io::cold_used, dim3(io_grid((size_t)n_chunks * v.pc)), dim3(io::kIoBlock), 0, s, v, flag);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(e->h_scal + 12, flag, 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(e->h_scal.p + 12, flag, 4, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
-  *out = *(uint32_t*)(e->h_scal + 12);
+  *out = *(uint32_t*)(e->h_scal.p + 12);
   return GR_OK;
 }
 
@@ -1206,14 +1222,144 @@ int gr_space_decode(const void* space_host, uint32_t n_chunks, uint32_t position
   return n <= cap || !out ? GR_OK : GR_ECAPACITY;
 }
 
+// The outbox mailboxes and lane results of the pass just launched, as compact
+// records (+ ext records where they do not fit), downloaded into engine-owned
+// pinned memory: gr_step_compact_end and gr_step_wire_compact.
+static int pack_out_compact(gr_engine* e, uint32_t nl, const SpaceView& vout, gr_coutbox* out, PhaseClock* cl,
+                            const gr_wire_out_cfg* wcfg, gr_wire_out* wout) {
+  PhaseClock& clk = *cl;
+  const uint32_t S = e->S;
+  const hipStream_t s = e->stream;
+  const dim3 blk(io::kIoBlock);
+  int r;
+  uint32_t* scal = (uint32_t*)e->d_scal.p;
+  uint32_t* peer_of_lane = e->ln.u32(LR_LANE_PEER);
+  // ---- outbox mailboxes + lane results -> compact records (+ ext)
+  if ((r = e->d_oc64.grow((size_t)nl * 8))) return r;
+  if ((r = e->d_off64.grow((size_t)nl * 8))) return r;
+  if ((r = e->d_rx.grow((size_t)nl * 4))) return r;
+  if ((r = e->d_roff.grow((size_t)nl * 4))) return r;
+  if ((r = e->d_results.grow((size_t)nl * sizeof(gr_cresult)))) return r;
+  uint64_t* oc = (uint64_t*)e->d_oc64.p;
+  uint64_t* off = (uint64_t*)e->d_off64.p;
+  uint32_t* rx = (uint32_t*)e->d_rx.p;
+  uint32_t* roff = (uint32_t*)e->d_roff.p;
+  // ---- gr_step_wire_out: the entry-free mailboxes leave as MessageBatch records
+  // (gr_io.h wire_out_*): classified and ranked first, so the compact pack skips them
+  const uint8_t* wf = nullptr;
+  const uint32_t T = e->n_targets, nblk = (nl + io::kIoBlock - 1) / io::kIoBlock;
+  if (wout) {
+    const size_t pairs = (size_t)nl * S, cells = (size_t)T * nblk;
+    if ((r = e->d_wf.grow(pairs))) return r;
+    if ((r = e->d_wrank.grow(pairs * 4))) return r;
+    if ((r = e->d_wcnt.grow(cells * 4))) return r;
+    if ((r = e->d_wbase.grow(cells * 4))) return r;
+    if ((r = e->d_wplan.grow((2 * (size_t)GR_MAX_TARGETS + 2) * 4))) return r;
+    if ((r = e->d_wtot.grow(8))) return r;
+    if ((r = e->h_wtot.grow(8))) return r;
+    const uint32_t* tgt = (const uint32_t*)e->d_target.p;
+    uint32_t* wrank = (uint32_t*)e->d_wrank.p;
+    uint32_t* wcnt = (uint32_t*)e->d_wcnt.p;
+    if ((r = with_slots(S, [&](auto ss) {
+          hipLaunchKernelGGL(io::wire_out_group<decltype(ss)::value>, dim3(nblk), blk, 0, s, vout, nl,
+                             (const uint32_t*)peer_of_lane, tgt, T, e->d_wf.as<uint8_t>(), wrank, wcnt);
+          return GR_OK;
+        })))
+      return r;
+    HIPCHK(hipGetLastError());
+    if ((r = io_scan(e, wcnt, (uint32_t*)e->d_wbase.p, (uint32_t)cells, s))) return r;
+    hipLaunchKernelGGL(io::wire_out_plan, dim3(1), blk, 0, s, (const uint32_t*)wcnt, (const uint32_t*)e->d_wbase.p, T,
+                       nblk, wcfg->max_batch_msgs, (uint32_t*)e->d_wplan.p, (uint32_t*)e->d_wtot.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(e->h_wtot.p, e->d_wtot.p, 8, hipMemcpyDeviceToHost, s));
+    wf = (const uint8_t*)e->d_wf.p;
+  }
+  hipLaunchKernelGGL(io::out_counts_c, dim3(io_grid(nl)), blk, 0, s, vout, e->ln, e->st, nl, S, oc, rx, wf);
+  HIPCHK(hipGetLastError());
+  if ((r = io_scan64(e, oc, off, nl, s))) return r;
+  if ((r = io_scan(e, rx, roff, nl, s))) return r;
+  hipLaunchKernelGGL(io::finish_total_c, dim3(1), dim3(64), 0, s, (const uint64_t*)oc, (const uint64_t*)off,
+                     (const uint32_t*)rx, (const uint32_t*)roff, nl, scal + 1);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(e->h_scal.p + 4, scal + 1, 12, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  clk.mark("mailboxes+pass+counts");
+  const uint32_t total = ((uint32_t*)e->h_scal.p)[1], text = ((uint32_t*)e->h_scal.p)[2], rext = ((uint32_t*)e->h_scal.p)[3];
+  const size_t mbytes = (size_t)total * sizeof(gr_cmsg), xbytes = (size_t)text * sizeof(gr_message);
+  const size_t rbytes = (size_t)nl * sizeof(gr_cresult), rxbytes = (size_t)rext * sizeof(gr_peer_result);
+  if ((r = e->d_outmsgs.grow(mbytes + 1))) return r;
+  if ((r = e->d_outext.grow(xbytes + 1))) return r;
+  if ((r = e->d_resext.grow(rxbytes + 1))) return r;
+  if ((r = e->h_outmsgs.grow(mbytes + 1))) return r;
+  if ((r = e->h_outext.grow(xbytes + 1))) return r;
+  if ((r = e->h_results.grow(rbytes))) return r;
+  if ((r = e->h_resext.grow(rxbytes + 1))) return r;
+  hipLaunchKernelGGL(io::pack_results_c, dim3(io_grid(nl)), blk, 0, s, e->ln, e->st, (const uint32_t*)peer_of_lane,
+                     nl, (const uint32_t*)roff, (gr_cresult*)e->d_results.p, (gr_peer_result*)e->d_resext.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(e->h_results.p, e->d_results.p, rbytes, hipMemcpyDeviceToHost, s));
+  if (rext) HIPCHK(hipMemcpyAsync(e->h_resext.p, e->d_resext.p, rxbytes, hipMemcpyDeviceToHost, s));
+  if (total) {
+    hipLaunchKernelGGL(io::pack_outbox_c, dim3(io_grid(nl)), blk, 0, s, vout, nl, S, (const uint64_t*)off,
+                       (const uint32_t*)peer_of_lane, (gr_cmsg*)e->d_outmsgs.p, (gr_message*)e->d_outext.p, wf);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(e->h_outmsgs.p, e->d_outmsgs.p, mbytes, hipMemcpyDeviceToHost, s));
+    if (text) HIPCHK(hipMemcpyAsync(e->h_outext.p, e->d_outext.p, xbytes, hipMemcpyDeviceToHost, s));
+  }
+  uint32_t wn = 0, wnb = 0;
+  if (wout) {  // the totals came down with the counts above
+    wn = ((uint32_t*)e->h_wtot.p)[0];
+    wnb = ((uint32_t*)e->h_wtot.p)[1];
+    if ((r = e->d_wmsgs.grow((size_t)wn * sizeof(grw_message) + 1))) return r;
+    if ((r = e->d_wbat.grow((size_t)wnb * sizeof(grw_batch) + 1))) return r;
+    if ((r = e->d_wbt.grow((size_t)wnb * 4 + 4))) return r;
+    if ((r = e->h_wbt.grow((size_t)wnb * 4 + 4))) return r;
+    if (wn) {
+      const uint32_t* tgt = (const uint32_t*)e->d_target.p;
+      const uint64_t* clu = (const uint64_t*)e->d_cluster.p;
+      const uint32_t* wrank = (const uint32_t*)e->d_wrank.p;
+      const uint32_t* wbase = (const uint32_t*)e->d_wbase.p;
+      const uint32_t* plan = (const uint32_t*)e->d_wplan.p;
+      const uint32_t mbm = wcfg->max_batch_msgs;
+      grw_message* wm = (grw_message*)e->d_wmsgs.p;
+      if ((r = with_slots(S, [&](auto ss) {
+            hipLaunchKernelGGL(io::wire_out_scatter<decltype(ss)::value>, dim3(nblk), blk, 0, s, vout, nl,
+                               (const uint32_t*)peer_of_lane, tgt, e->st, clu, wf, wrank, wbase, plan, T, mbm, wm);
+            return GR_OK;
+          })))
+        return r;
+      HIPCHK(hipGetLastError());
+      hipLaunchKernelGGL(io::wire_out_batches, dim3(io_grid(wnb)), blk, 0, s, plan, T, *wcfg, wnb,
+                         (grw_batch*)e->d_wbat.p, (uint32_t*)e->d_wbt.p);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipMemcpyAsync(e->h_wbt.p, e->d_wbt.p, (size_t)wnb * 4, hipMemcpyDeviceToHost, s));
+    }
+  }
+  HIPCHK(hipStreamSynchronize(s));
+  clk.mark("pack+download");
+  clk.report();
+  out->msgs = total ? (gr_cmsg*)e->h_outmsgs.p : nullptr;
+  out->n_msgs = total;
+  out->ext_msgs = text ? (gr_message*)e->h_outext.p : nullptr;
+  out->n_ext_msgs = text;
+  out->results = (gr_cresult*)e->h_results.p;
+  out->n_results = nl;
+  out->ext_results = rext ? (gr_peer_result*)e->h_resext.p : nullptr;
+  out->n_ext_results = rext;
+  if (wout) {
+    wout->d_batches = wnb ? (grw_batch*)e->d_wbat.p : nullptr;
+    wout->n_batches = wnb;
+    wout->d_msgs = wn ? (const grw_message*)e->d_wmsgs.p : nullptr;
+    wout->n_msgs = wn;
+    wout->batch_target = wnb ? (const uint32_t*)e->h_wbt.p : nullptr;
+  }
+  return GR_OK;
+}
+
 // The device pass of gr_step over nm gr_message records already in e->d_msgs
 // (copied from the host by gr_step, or routed from decoded wire records by
-// gr_step_wire) and nlc host local inputs. Caller holds e->mu.
-static int pack_out_compact(gr_engine* e, uint32_t nl, const SpaceView& vout, gr_coutbox* out, PhaseClock* cl,
-                            const gr_wire_out_cfg* wcfg = nullptr, gr_wire_out* wout = nullptr);
-
-// gr_step's device pipeline from inbox records in HBM (e->d_msgs); the outbox as
-// full records (out) or, with cout, as compact records (gr_step_wire_compact)
+// gr_step_wire) and nlc host local inputs; the outbox as full records (out) or,
+// with cout, as compact records (gr_step_wire_compact). Caller holds e->mu.
 static int step_staged(gr_engine* e, uint32_t nm, const gr_local_input* locals, uint32_t nlc, gr_outbox* out,
                        gr_coutbox* cout = nullptr, const gr_wire_out_cfg* wcfg = nullptr,
                        gr_wire_out* wout = nullptr) {
@@ -1224,96 +1370,31 @@ static int step_staged(gr_engine* e, uint32_t nm, const gr_local_input* locals, 
     out->n_results = 0;
   }
   if (cout) memset(cout, 0, sizeof(*cout));
-  const uint32_t S = e->S, cap = e->cfg.max_peers;
   if (nm + nlc == 0) return GR_OK;
+  const uint32_t S = e->S;
   const hipStream_t s = e->stream;
   const dim3 blk(io::kIoBlock);
   int r;
-  // ---- inbox records -> lanes (gr_io.h)
-  if ((r = grow_device(&e->d_locals.p, &e->d_locals.n, (size_t)nlc * sizeof(gr_local_input) + 1))) return r;
-  if ((r = grow_device(&e->d_mark.p, &e->d_mark.n, (size_t)cap * 4))) return r;
-  if ((r = grow_device(&e->d_lop.p, &e->d_lop.n, (size_t)cap * 4))) return r;
-  if ((r = grow_device(&e->d_scal.p, &e->d_scal.n, 16))) return r;
-  if ((r = grow_pinned(&e->h_scal, &e->h_scal_bytes, 16))) return r;
-  uint32_t* mark = (uint32_t*)e->d_mark.p;
-  uint32_t* lop = (uint32_t*)e->d_lop.p;
-  uint32_t* scal = (uint32_t*)e->d_scal.p;
-  const gr_message* dmsgs = (const gr_message*)e->d_msgs.p;
-  const gr_local_input* dloc = (const gr_local_input*)e->d_locals.p;
+  if ((r = e->d_locals.grow((size_t)nlc * sizeof(gr_local_input) + 1))) return r;
   if (nlc)
     HIPCHK(hipMemcpyAsync(e->d_locals.p, locals, (size_t)nlc * sizeof(gr_local_input), hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemsetAsync(mark, 0, (size_t)cap * 4, s));
-  HIPCHK(hipMemsetAsync(scal, 0, 16, s));
-  if (e->quiesce && nlc) {  // ticks are LocalTicks: a QuiescedTick count is refused (scal[1], read below)
-    hipLaunchKernelGGL(io::check_raw_ticks, dim3(io_grid(nlc)), blk, 0, s, dloc, nlc, scal + 1);
-    HIPCHK(hipGetLastError());
-  }
-  hipLaunchKernelGGL(io::mark_inputs, dim3(io_grid(nm + nlc)), blk, 0, s, dmsgs, nm, dloc, nlc, S, cap, mark,
-                     scal + 1, (uint32_t)e->config_entries);
-  HIPCHK(hipGetLastError());
-  if ((r = io_scan(e, mark, lop, cap, s))) return r;
-  hipLaunchKernelGGL(io::finish_lanes, dim3(1), dim3(64), 0, s, (const uint32_t*)mark, (const uint32_t*)lop, cap,
-                     (const uint32_t*)(scal + 1), scal);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(e->h_scal, scal, 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  const uint32_t nl = ((uint32_t*)e->h_scal)[0];
-  if (((uint32_t*)e->h_scal)[1]) return GR_EINVAL;  // nothing of the pass ran
+  const FullInbox in{e->d_msgs.as<const gr_message>(), nm, e->d_locals.as<const gr_local_input>(), nlc};
+  uint32_t nl, err;
+  if ((r = stage_lanes(e, in, &nl, &err))) return r;
+  if (err) return GR_EINVAL;  // nothing of the pass ran
   if (nl == 0) return GR_OK;
-  uint32_t* peer_of_lane = e->ln.u32(LR_LANE_PEER);
-  hipLaunchKernelGGL(io::lane_peers, dim3(io_grid(cap)), blk, 0, s, (const uint32_t*)mark, (const uint32_t*)lop, cap,
-                     peer_of_lane);
-  HIPCHK(hipGetLastError());
-  // ---- mailboxes: slot-major j*nl + lane, arrival order kept by a stable sort
-  const uint32_t positions = nl * S;
-  const size_t space = gr_space_bytes(1, positions, GR_C);
-  if ((r = grow_device(&e->d_in.p, &e->d_in.n, space))) return r;
-  if ((r = grow_device(&e->d_out.p, &e->d_out.n, space))) return r;
-  const SpaceView vin = make_view(e->d_in.p, 1, positions), vout = make_view(e->d_out.p, 1, positions);
-  hipLaunchKernelGGL(io::clear_counts, dim3(io_grid(vin.pc)), blk, 0, s, vin, vin.pc);  // the count bytes
-  HIPCHK(hipGetLastError());
-  if (nm) {
-    for (gr_engine::Buf* b : {&e->d_keys, &e->d_idx, &e->d_skeys, &e->d_sidx})
-      if ((r = grow_device(&b->p, &b->n, (size_t)nm * 4))) return r;
-    hipLaunchKernelGGL(io::msg_keys, dim3(io_grid(nm)), blk, 0, s, dmsgs, nm, (const uint32_t*)lop, nl,
-                       (uint32_t*)e->d_keys.p, (uint32_t*)e->d_idx.p);
-    HIPCHK(hipGetLastError());
-    if ((r = sort_keys(e, nm, positions, s))) return r;
-    hipLaunchKernelGGL(io::encode_sorted, dim3(io_grid(nm)), blk, 0, s, dmsgs, (const uint32_t*)e->d_skeys.p,
-                       (const uint32_t*)e->d_sidx.p, nm, vin, (uint32_t)e->config_entries);
-    HIPCHK(hipGetLastError());
-  }
-  // ---- locals -> lane rows
-  if ((r = grow_device(&e->d_win.p, &e->d_win.n, (size_t)nl * 4))) return r;
-  HIPCHK(hipMemsetAsync(e->d_win.p, 0, (size_t)nl * 4, s));
-  if (nlc) {
-    hipLaunchKernelGGL(io::local_winner, dim3(io_grid(nlc)), blk, 0, s, dloc, nlc, (const uint32_t*)lop,
-                       (uint32_t*)e->d_win.p);
-    HIPCHK(hipGetLastError());
-  }
-  hipLaunchKernelGGL(io::fill_locals, dim3(io_grid(nl)), blk, 0, s, dloc, (const uint32_t*)e->d_win.p, nl, e->ln);
-  HIPCHK(hipGetLastError());
-  // ---- the pass
-  StepParams kp = base_params(e);
-  kp.has_locals = 1;
-  kp.has_lane_peer = 1;
-  kp.route_mode = RT_IDENTITY;
-  kp.in = vin;
-  kp.out = vout;
-  kp.n_lanes = nl;
-  kp.qraw = e->ln.u32(LR_TICKS);  // this pass's rows are the raw input: the quiesce pass rewrites them in place
-  HIPCHK(launch_slots(S, kp, e->bail, e->counters, e->cap, (uint32_t)e->launches++, s, next_timing(e)));
-  e->passes++;
-  e->locals_set = false;    // the lane rows now hold this pass's compact locals
-  e->routes_bound = false;  // and RT_IDENTITY replaced the bound routes
+  SpaceView vout;
+  if ((r = run_staged_pass(e, in, nl, &vout))) return r;
   if (cout) {
     PhaseClock clk;
     return pack_out_compact(e, nl, vout, cout, &clk, wcfg, wout);
   }
+  uint32_t* scal = e->d_scal.as<uint32_t>();
+  uint32_t* peer_of_lane = e->ln.u32(LR_LANE_PEER);
   // ---- outbox mailboxes + lane results -> records
-  if ((r = grow_device(&e->d_oc.p, &e->d_oc.n, (size_t)nl * 4))) return r;
-  if ((r = grow_device(&e->d_off.p, &e->d_off.n, (size_t)nl * 4))) return r;
-  if ((r = grow_device(&e->d_results.p, &e->d_results.n, (size_t)nl * sizeof(gr_peer_result)))) return r;
+  if ((r = e->d_oc.grow((size_t)nl * 4))) return r;
+  if ((r = e->d_off.grow((size_t)nl * 4))) return r;
+  if ((r = e->d_results.grow((size_t)nl * sizeof(gr_peer_result)))) return r;
   uint32_t* oc = (uint32_t*)e->d_oc.p;
   uint32_t* off = (uint32_t*)e->d_off.p;
   hipLaunchKernelGGL(io::out_counts, dim3(io_grid(nl)), blk, 0, s, vout, nl, S, oc);
@@ -1324,24 +1405,24 @@ static int step_staged(gr_engine* e, uint32_t nm, const gr_local_input* locals, 
   hipLaunchKernelGGL(io::pack_results, dim3(io_grid(nl)), blk, 0, s, e->ln, e->st, (const uint32_t*)peer_of_lane,
                      0u, nl, (gr_peer_result*)e->d_results.p);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(e->h_scal + 8, scal + 2, 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(e->h_scal.p + 8, scal + 2, 4, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
-  const uint32_t total = ((uint32_t*)e->h_scal)[2];
+  const uint32_t total = ((uint32_t*)e->h_scal.p)[2];
   const size_t mbytes = (size_t)total * sizeof(gr_message), rbytes = (size_t)nl * sizeof(gr_peer_result);
-  if ((r = grow_device(&e->d_outmsgs.p, &e->d_outmsgs.n, mbytes + 1))) return r;
-  if ((r = grow_pinned(&e->h_outmsgs, &e->h_outmsgs_bytes, mbytes + 1))) return r;
-  if ((r = grow_pinned(&e->h_results, &e->h_results_bytes, rbytes))) return r;
+  if ((r = e->d_outmsgs.grow(mbytes + 1))) return r;
+  if ((r = e->h_outmsgs.grow(mbytes + 1))) return r;
+  if ((r = e->h_results.grow(rbytes))) return r;
   if (total) {
     hipLaunchKernelGGL(io::pack_outbox, dim3(io_grid(nl)), blk, 0, s, vout, nl, S, (const uint32_t*)off,
                        (const uint32_t*)peer_of_lane, (gr_message*)e->d_outmsgs.p);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(e->h_outmsgs, e->d_outmsgs.p, mbytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(e->h_outmsgs.p, e->d_outmsgs.p, mbytes, hipMemcpyDeviceToHost, s));
   }
-  HIPCHK(hipMemcpyAsync(e->h_results, e->d_results.p, rbytes, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(e->h_results.p, e->d_results.p, rbytes, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
-  out->msgs = total ? (gr_message*)e->h_outmsgs : nullptr;
+  out->msgs = total ? (gr_message*)e->h_outmsgs.p : nullptr;
   out->n_msgs = total;
-  out->results = (gr_peer_result*)e->h_results;
+  out->results = (gr_peer_result*)e->h_results.p;
   out->n_results = nl;
   return GR_OK;
 }
@@ -1354,7 +1435,7 @@ int gr_step(gr_engine* e, const gr_inbox* in, gr_outbox* out) {
   GR_REFUSE_PENDING(e);
   const uint32_t nm = (uint32_t)in->n_msgs;
   int r;
-  if ((r = grow_device(&e->d_msgs.p, &e->d_msgs.n, (size_t)nm * sizeof(gr_message) + 1))) return r;
+  if ((r = e->d_msgs.grow((size_t)nm * sizeof(gr_message) + 1))) return r;
   if (nm)
     HIPCHK(hipMemcpyAsync(e->d_msgs.p, in->msgs, (size_t)nm * sizeof(gr_message), hipMemcpyHostToDevice, e->stream));
   return step_staged(e, nm, in->locals, (uint32_t)in->n_locals, out);
@@ -1381,11 +1462,11 @@ int gr_bind_nodes(gr_engine* e, const uint64_t* cluster_ids, const uint64_t* nod
     t[h].peer = p;
   }
   int r;
-  if ((r = grow_device(&e->d_nodes.p, &e->d_nodes.n, (size_t)tcap * sizeof(io::NodeKey)))) return r;
+  if ((r = e->d_nodes.grow((size_t)tcap * sizeof(io::NodeKey)))) return r;
   HIPCHK(hipMemcpy(e->d_nodes.p, t.data(), (size_t)tcap * sizeof(io::NodeKey), hipMemcpyHostToDevice));
   // the cluster id of every slot (0 above n): the outbound records' ClusterID
   const size_t cap = e->cfg.max_peers;
-  if ((r = grow_device(&e->d_cluster.p, &e->d_cluster.n, cap * 8 + 8))) return r;
+  if ((r = e->d_cluster.grow(cap * 8 + 8))) return r;
   HIPCHK(hipMemset(e->d_cluster.p, 0, cap * 8));
   if (n) HIPCHK(hipMemcpy(e->d_cluster.p, cluster_ids, (size_t)n * 8, hipMemcpyHostToDevice));
   e->nodes_cap = tcap;
@@ -1407,18 +1488,10 @@ int gr_bind_targets(gr_engine* e, const uint32_t* target_of, uint32_t n_peers, u
   for (uint32_t p = 0; p < n_peers; ++p)
     std::copy(target_of + (size_t)p * slots, target_of + (size_t)(p + 1) * slots, t.begin() + (size_t)p * S);
   int r;
-  if ((r = grow_device(&e->d_target.p, &e->d_target.n, all * 4 + 4))) return r;
+  if ((r = e->d_target.grow(all * 4 + 4))) return r;
   HIPCHK(hipMemcpy(e->d_target.p, t.data(), all * 4, hipMemcpyHostToDevice));
   e->n_targets = n_targets;
   return GR_OK;
-}
-
-extern "C++" template <int S>
-static void launch_route_wire(const grw_message* wm, uint32_t n, const grw_entry* we, uint64_t n_ents,
-                              const io::NodeKey* nodes, uint32_t tcap, StateBase st, gr_message* out,
-                              uint32_t* flag, uint8_t* why, uint32_t ce, hipStream_t s) {
-  hipLaunchKernelGGL((io::route_wire<S>), dim3(io_grid(n)), dim3(io::kIoBlock), 0, s, wm, n, we, n_ents, nodes, tcap,
-                     st, out, flag, why, ce);
 }
 
 // The wire path's routing half (gr_step_wire, gr_step_wire_compact): decoded
@@ -1435,46 +1508,41 @@ static int wire_route(gr_engine* e, const struct grw_message* d_msgs, size_t n_m
   const hipStream_t s = e->stream;
   const dim3 blk(io::kIoBlock);
   int r;
-  if ((r = grow_device(&e->d_msgs.p, &e->d_msgs.n, (size_t)nw * sizeof(gr_message) + 1))) return r;
+  if ((r = e->d_msgs.grow((size_t)nw * sizeof(gr_message) + 1))) return r;
   uint32_t nm = 0;
   if (nw) {
     // route every decoded message to (slot, sender slot) in a gr_message record,
     // then keep the routed ones in wire order (their arrival order)
-    if ((r = grow_device(&e->d_wrec.p, &e->d_wrec.n, (size_t)nw * sizeof(gr_message)))) return r;
-    if ((r = grow_device(&e->d_keys.p, &e->d_keys.n, (size_t)nw * 4 + 4))) return r;
-    if ((r = grow_device(&e->d_idx.p, &e->d_idx.n, (size_t)nw * 4 + 4))) return r;
-    if ((r = grow_device(&e->d_why.p, &e->d_why.n, (size_t)nw + 1))) return r;
-    if ((r = grow_device(&e->d_unr.p, &e->d_unr.n, (size_t)nw * 4 + 4))) return r;
-    if ((r = grow_device(&e->d_scal.p, &e->d_scal.n, 16))) return r;
-    if ((r = grow_pinned(&e->h_scal, &e->h_scal_bytes, 16))) return r;
+    if ((r = e->d_wrec.grow((size_t)nw * sizeof(gr_message)))) return r;
+    if ((r = e->d_keys.grow((size_t)nw * 4 + 4))) return r;
+    if ((r = e->d_idx.grow((size_t)nw * 4 + 4))) return r;
+    if ((r = e->d_why.grow((size_t)nw + 1))) return r;
+    if ((r = e->d_unr.grow((size_t)nw * 4 + 4))) return r;
+    if ((r = ensure_scal(e))) return r;
     uint32_t* flag = (uint32_t*)e->d_keys.p;
     uint32_t* pos = (uint32_t*)e->d_idx.p;
     uint32_t* scal = (uint32_t*)e->d_scal.p;
-    switch (e->S) {
-      case 1: launch_route_wire<1>(d_msgs, nw, d_ents, n_ents, (const io::NodeKey*)e->d_nodes.p, e->nodes_cap, e->st,
-                                   (gr_message*)e->d_wrec.p, flag, (uint8_t*)e->d_why.p, e->config_entries, s); break;
-      case 3: launch_route_wire<3>(d_msgs, nw, d_ents, n_ents, (const io::NodeKey*)e->d_nodes.p, e->nodes_cap, e->st,
-                                   (gr_message*)e->d_wrec.p, flag, (uint8_t*)e->d_why.p, e->config_entries, s); break;
-      case 5: launch_route_wire<5>(d_msgs, nw, d_ents, n_ents, (const io::NodeKey*)e->d_nodes.p, e->nodes_cap, e->st,
-                                   (gr_message*)e->d_wrec.p, flag, (uint8_t*)e->d_why.p, e->config_entries, s); break;
-      default: launch_route_wire<GR_SMAX>(d_msgs, nw, d_ents, n_ents, (const io::NodeKey*)e->d_nodes.p,
-                                          e->nodes_cap, e->st, (gr_message*)e->d_wrec.p, flag,
-                                          (uint8_t*)e->d_why.p, e->config_entries, s); break;
-    }
+    if ((r = with_slots(e->S, [&](auto ss) {
+          hipLaunchKernelGGL(io::route_wire<decltype(ss)::value>, dim3(io_grid(nw)), blk, 0, s, d_msgs, nw, d_ents,
+                             (uint64_t)n_ents, e->d_nodes.as<const io::NodeKey>(), e->nodes_cap, e->st,
+                             e->d_wrec.as<gr_message>(), flag, e->d_why.as<uint8_t>(), (uint32_t)e->config_entries);
+          return GR_OK;
+        })))
+      return r;
     HIPCHK(hipGetLastError());
     if ((r = io_scan(e, flag, pos, nw, s))) return r;
     hipLaunchKernelGGL(io::keep_routed, dim3(io_grid(nw)), blk, 0, s, (const gr_message*)e->d_wrec.p,
                        (const uint32_t*)flag, (const uint32_t*)pos, nw, (gr_message*)e->d_msgs.p,
                        (uint32_t*)e->d_unr.p, scal);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(e->h_scal, scal, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(e->h_scal.p, scal, 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    nm = ((uint32_t*)e->h_scal)[0];
+    nm = ((uint32_t*)e->h_scal.p)[0];
     const uint32_t nu = nw - nm;
     if (nu) {  // the messages the host steps with the Go code, in wire order, and why
-      if ((r = grow_pinned(&e->h_unr, &e->h_unr_bytes, (size_t)nu * 5))) return r;
-      uint32_t* hidx = (uint32_t*)e->h_unr;
-      uint8_t* hwhy = e->h_unr + (size_t)nu * 4;
+      if ((r = e->h_unr.grow((size_t)nu * 5))) return r;
+      uint32_t* hidx = (uint32_t*)e->h_unr.p;
+      uint8_t* hwhy = e->h_unr.p + (size_t)nu * 4;
       HIPCHK(hipMemcpyAsync(hidx, e->d_unr.p, (size_t)nu * 4, hipMemcpyDeviceToHost, s));
       std::vector<uint8_t> allwhy(nw);
       HIPCHK(hipMemcpyAsync(allwhy.data(), e->d_why.p, nw, hipMemcpyDeviceToHost, s));
@@ -1530,157 +1598,6 @@ int gr_step_wire_out(gr_engine* e, const struct grw_message* d_msgs, size_t n_ms
   return step_staged(e, nm, locals, (uint32_t)n_locals, nullptr, out, cfg, wout);
 }
 
-extern "C++" template <int S>
-static void launch_wire_out_group(const SpaceView& vout, uint32_t nl, uint32_t nblk, const uint32_t* pol,
-                                  const uint32_t* target_of, uint32_t T, uint8_t* wf, uint32_t* rank, uint32_t* cnt,
-                                  hipStream_t s) {
-  hipLaunchKernelGGL((io::wire_out_group<S>), dim3(nblk), dim3(io::kIoBlock), 0, s, vout, nl, pol, target_of, T, wf,
-                     rank, cnt);
-}
-extern "C++" template <int S>
-static void launch_wire_out_scatter(const SpaceView& vout, uint32_t nl, uint32_t nblk, const uint32_t* pol,
-                                    const uint32_t* target_of, StateBase st, const uint64_t* cluster_of,
-                                    const uint8_t* wf, const uint32_t* rank, const uint32_t* base,
-                                    const uint32_t* plan, uint32_t T, uint32_t mbm, grw_message* wmsgs,
-                                    hipStream_t s) {
-  hipLaunchKernelGGL((io::wire_out_scatter<S>), dim3(nblk), dim3(io::kIoBlock), 0, s, vout, nl, pol, target_of, st,
-                     cluster_of, wf, rank, base, plan, T, mbm, wmsgs);
-}
-
-// The outbox mailboxes and lane results of the pass just launched, as compact
-// records (+ ext records where they do not fit), downloaded into engine-owned
-// pinned memory: gr_step_compact_end and gr_step_wire_compact.
-static int pack_out_compact(gr_engine* e, uint32_t nl, const SpaceView& vout, gr_coutbox* out, PhaseClock* cl,
-                            const gr_wire_out_cfg* wcfg, gr_wire_out* wout) {
-  PhaseClock& clk = *cl;
-  const uint32_t S = e->S;
-  const hipStream_t s = e->stream;
-  const dim3 blk(io::kIoBlock);
-  int r;
-  uint32_t* scal = (uint32_t*)e->d_scal.p;
-  uint32_t* peer_of_lane = e->ln.u32(LR_LANE_PEER);
-  // ---- outbox mailboxes + lane results -> compact records (+ ext)
-  if ((r = grow_device(&e->d_oc64.p, &e->d_oc64.n, (size_t)nl * 8))) return r;
-  if ((r = grow_device(&e->d_off64.p, &e->d_off64.n, (size_t)nl * 8))) return r;
-  if ((r = grow_device(&e->d_rx.p, &e->d_rx.n, (size_t)nl * 4))) return r;
-  if ((r = grow_device(&e->d_roff.p, &e->d_roff.n, (size_t)nl * 4))) return r;
-  if ((r = grow_device(&e->d_results.p, &e->d_results.n, (size_t)nl * sizeof(gr_cresult)))) return r;
-  uint64_t* oc = (uint64_t*)e->d_oc64.p;
-  uint64_t* off = (uint64_t*)e->d_off64.p;
-  uint32_t* rx = (uint32_t*)e->d_rx.p;
-  uint32_t* roff = (uint32_t*)e->d_roff.p;
-  // ---- gr_step_wire_out: the entry-free mailboxes leave as MessageBatch records
-  // (gr_io.h wire_out_*): classified and ranked first, so the compact pack skips them
-  const uint8_t* wf = nullptr;
-  const uint32_t T = e->n_targets, nblk = (nl + io::kIoBlock - 1) / io::kIoBlock;
-  if (wout) {
-    const size_t pairs = (size_t)nl * S, cells = (size_t)T * nblk;
-    if ((r = grow_device(&e->d_wf.p, &e->d_wf.n, pairs))) return r;
-    if ((r = grow_device(&e->d_wrank.p, &e->d_wrank.n, pairs * 4))) return r;
-    if ((r = grow_device(&e->d_wcnt.p, &e->d_wcnt.n, cells * 4))) return r;
-    if ((r = grow_device(&e->d_wbase.p, &e->d_wbase.n, cells * 4))) return r;
-    if ((r = grow_device(&e->d_wplan.p, &e->d_wplan.n, (2 * (size_t)GR_MAX_TARGETS + 2) * 4))) return r;
-    if ((r = grow_device(&e->d_wtot.p, &e->d_wtot.n, 8))) return r;
-    if ((r = grow_pinned(&e->h_wtot, &e->h_wtot_bytes, 8))) return r;
-    const uint32_t* tgt = (const uint32_t*)e->d_target.p;
-    uint32_t* wrank = (uint32_t*)e->d_wrank.p;
-    uint32_t* wcnt = (uint32_t*)e->d_wcnt.p;
-    switch (S) {
-      case 1: launch_wire_out_group<1>(vout, nl, nblk, peer_of_lane, tgt, T, (uint8_t*)e->d_wf.p, wrank, wcnt, s); break;
-      case 3: launch_wire_out_group<3>(vout, nl, nblk, peer_of_lane, tgt, T, (uint8_t*)e->d_wf.p, wrank, wcnt, s); break;
-      case 5: launch_wire_out_group<5>(vout, nl, nblk, peer_of_lane, tgt, T, (uint8_t*)e->d_wf.p, wrank, wcnt, s); break;
-      default: launch_wire_out_group<GR_SMAX>(vout, nl, nblk, peer_of_lane, tgt, T, (uint8_t*)e->d_wf.p, wrank, wcnt, s); break;
-    }
-    HIPCHK(hipGetLastError());
-    if ((r = io_scan(e, wcnt, (uint32_t*)e->d_wbase.p, (uint32_t)cells, s))) return r;
-    hipLaunchKernelGGL(io::wire_out_plan, dim3(1), blk, 0, s, (const uint32_t*)wcnt, (const uint32_t*)e->d_wbase.p, T,
-                       nblk, wcfg->max_batch_msgs, (uint32_t*)e->d_wplan.p, (uint32_t*)e->d_wtot.p);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(e->h_wtot, e->d_wtot.p, 8, hipMemcpyDeviceToHost, s));
-    wf = (const uint8_t*)e->d_wf.p;
-  }
-  hipLaunchKernelGGL(io::out_counts_c, dim3(io_grid(nl)), blk, 0, s, vout, e->ln, e->st, nl, S, oc, rx, wf);
-  HIPCHK(hipGetLastError());
-  if ((r = io_scan64(e, oc, off, nl, s))) return r;
-  if ((r = io_scan(e, rx, roff, nl, s))) return r;
-  hipLaunchKernelGGL(io::finish_total_c, dim3(1), dim3(64), 0, s, (const uint64_t*)oc, (const uint64_t*)off,
-                     (const uint32_t*)rx, (const uint32_t*)roff, nl, scal + 1);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(e->h_scal + 4, scal + 1, 12, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  clk.mark("mailboxes+pass+counts");
-  const uint32_t total = ((uint32_t*)e->h_scal)[1], text = ((uint32_t*)e->h_scal)[2], rext = ((uint32_t*)e->h_scal)[3];
-  const size_t mbytes = (size_t)total * sizeof(gr_cmsg), xbytes = (size_t)text * sizeof(gr_message);
-  const size_t rbytes = (size_t)nl * sizeof(gr_cresult), rxbytes = (size_t)rext * sizeof(gr_peer_result);
-  if ((r = grow_device(&e->d_outmsgs.p, &e->d_outmsgs.n, mbytes + 1))) return r;
-  if ((r = grow_device(&e->d_outext.p, &e->d_outext.n, xbytes + 1))) return r;
-  if ((r = grow_device(&e->d_resext.p, &e->d_resext.n, rxbytes + 1))) return r;
-  if ((r = grow_pinned(&e->h_outmsgs, &e->h_outmsgs_bytes, mbytes + 1))) return r;
-  if ((r = grow_pinned(&e->h_outext, &e->h_outext_bytes, xbytes + 1))) return r;
-  if ((r = grow_pinned(&e->h_results, &e->h_results_bytes, rbytes))) return r;
-  if ((r = grow_pinned(&e->h_resext, &e->h_resext_bytes, rxbytes + 1))) return r;
-  hipLaunchKernelGGL(io::pack_results_c, dim3(io_grid(nl)), blk, 0, s, e->ln, e->st, (const uint32_t*)peer_of_lane,
-                     nl, (const uint32_t*)roff, (gr_cresult*)e->d_results.p, (gr_peer_result*)e->d_resext.p);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(e->h_results, e->d_results.p, rbytes, hipMemcpyDeviceToHost, s));
-  if (rext) HIPCHK(hipMemcpyAsync(e->h_resext, e->d_resext.p, rxbytes, hipMemcpyDeviceToHost, s));
-  if (total) {
-    hipLaunchKernelGGL(io::pack_outbox_c, dim3(io_grid(nl)), blk, 0, s, vout, nl, S, (const uint64_t*)off,
-                       (const uint32_t*)peer_of_lane, (gr_cmsg*)e->d_outmsgs.p, (gr_message*)e->d_outext.p, wf);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(e->h_outmsgs, e->d_outmsgs.p, mbytes, hipMemcpyDeviceToHost, s));
-    if (text) HIPCHK(hipMemcpyAsync(e->h_outext, e->d_outext.p, xbytes, hipMemcpyDeviceToHost, s));
-  }
-  uint32_t wn = 0, wnb = 0;
-  if (wout) {  // the totals came down with the counts above
-    wn = ((uint32_t*)e->h_wtot)[0];
-    wnb = ((uint32_t*)e->h_wtot)[1];
-    if ((r = grow_device(&e->d_wmsgs.p, &e->d_wmsgs.n, (size_t)wn * sizeof(grw_message) + 1))) return r;
-    if ((r = grow_device(&e->d_wbat.p, &e->d_wbat.n, (size_t)wnb * sizeof(grw_batch) + 1))) return r;
-    if ((r = grow_device(&e->d_wbt.p, &e->d_wbt.n, (size_t)wnb * 4 + 4))) return r;
-    if ((r = grow_pinned(&e->h_wbt, &e->h_wbt_bytes, (size_t)wnb * 4 + 4))) return r;
-    if (wn) {
-      const uint32_t* tgt = (const uint32_t*)e->d_target.p;
-      const uint64_t* clu = (const uint64_t*)e->d_cluster.p;
-      const uint32_t* wrank = (const uint32_t*)e->d_wrank.p;
-      const uint32_t* wbase = (const uint32_t*)e->d_wbase.p;
-      const uint32_t* plan = (const uint32_t*)e->d_wplan.p;
-      const uint32_t mbm = wcfg->max_batch_msgs;
-      grw_message* wm = (grw_message*)e->d_wmsgs.p;
-      switch (S) {
-        case 1: launch_wire_out_scatter<1>(vout, nl, nblk, peer_of_lane, tgt, e->st, clu, wf, wrank, wbase, plan, T, mbm, wm, s); break;
-        case 3: launch_wire_out_scatter<3>(vout, nl, nblk, peer_of_lane, tgt, e->st, clu, wf, wrank, wbase, plan, T, mbm, wm, s); break;
-        case 5: launch_wire_out_scatter<5>(vout, nl, nblk, peer_of_lane, tgt, e->st, clu, wf, wrank, wbase, plan, T, mbm, wm, s); break;
-        default: launch_wire_out_scatter<GR_SMAX>(vout, nl, nblk, peer_of_lane, tgt, e->st, clu, wf, wrank, wbase, plan, T, mbm, wm, s); break;
-      }
-      HIPCHK(hipGetLastError());
-      hipLaunchKernelGGL(io::wire_out_batches, dim3(io_grid(wnb)), blk, 0, s, plan, T, *wcfg, wnb,
-                         (grw_batch*)e->d_wbat.p, (uint32_t*)e->d_wbt.p);
-      HIPCHK(hipGetLastError());
-      HIPCHK(hipMemcpyAsync(e->h_wbt, e->d_wbt.p, (size_t)wnb * 4, hipMemcpyDeviceToHost, s));
-    }
-  }
-  HIPCHK(hipStreamSynchronize(s));
-  clk.mark("pack+download");
-  clk.report();
-  out->msgs = total ? (gr_cmsg*)e->h_outmsgs : nullptr;
-  out->n_msgs = total;
-  out->ext_msgs = text ? (gr_message*)e->h_outext : nullptr;
-  out->n_ext_msgs = text;
-  out->results = (gr_cresult*)e->h_results;
-  out->n_results = nl;
-  out->ext_results = rext ? (gr_peer_result*)e->h_resext : nullptr;
-  out->n_ext_results = rext;
-  if (wout) {
-    wout->d_batches = wnb ? (grw_batch*)e->d_wbat.p : nullptr;
-    wout->n_batches = wnb;
-    wout->d_msgs = wn ? (const grw_message*)e->d_wmsgs.p : nullptr;
-    wout->n_msgs = wn;
-    wout->batch_target = wnb ? (const uint32_t*)e->h_wbt : nullptr;
-  }
-  return GR_OK;
-}
-
 // gr_step with compact records (gpuraft.h gr_cmsg / gr_clocal / gr_cresult):
 // the same device passes; records expand in registers on the way in and are
 // packed (with ext records for what does not fit) on the way out.
@@ -1702,7 +1619,6 @@ static int compact_begin_locked(gr_engine* e, const gr_cinbox* in) {
   if (e->cpend.on) return GR_EINVAL;  // the previous begin was not ended
   GR_REFUSE_PENDING(e);
   PhaseClock clk;  // GR_PHASES=1: per-phase host times on stderr
-  const uint32_t S = e->S, cap = e->cfg.max_peers;
   const uint32_t nm = (uint32_t)in->n_msgs, nlc = (uint32_t)in->n_locals;
   const uint32_t nx = (uint32_t)in->n_ext_msgs, nlx = (uint32_t)in->n_ext_locals;
   e->cpend = gr_engine::CPending{};
@@ -1712,52 +1628,20 @@ static int compact_begin_locked(gr_engine* e, const gr_cinbox* in) {
     return GR_OK;
   }
   const hipStream_t s = e->stream;
-  const dim3 blk(io::kIoBlock);
   int r;
-  // ---- inbox records -> lanes
-  if ((r = grow_device(&e->d_msgs.p, &e->d_msgs.n, (size_t)nm * sizeof(gr_cmsg) + 1))) return r;
-  if ((r = grow_device(&e->d_locals.p, &e->d_locals.n, (size_t)nlc * sizeof(gr_clocal) + 1))) return r;
-  if ((r = grow_device(&e->d_ext.p, &e->d_ext.n, (size_t)nx * sizeof(gr_message) + 1))) return r;
-  if ((r = grow_device(&e->d_lext.p, &e->d_lext.n, (size_t)nlx * sizeof(gr_local_input) + 1))) return r;
-  if ((r = grow_device(&e->d_mark.p, &e->d_mark.n, (size_t)cap * 4))) return r;
-  if ((r = grow_device(&e->d_lop.p, &e->d_lop.n, (size_t)cap * 4))) return r;
-  if ((r = grow_device(&e->d_scal.p, &e->d_scal.n, 16))) return r;
-  if ((r = grow_pinned(&e->h_scal, &e->h_scal_bytes, 16))) return r;
-  uint32_t* mark = (uint32_t*)e->d_mark.p;
-  uint32_t* lop = (uint32_t*)e->d_lop.p;
-  uint32_t* scal = (uint32_t*)e->d_scal.p;
-  io::CInbox ci;
-  ci.msgs = (const gr_cmsg*)e->d_msgs.p;
-  ci.ext = (const gr_message*)e->d_ext.p;
-  ci.loc = (const gr_clocal*)e->d_locals.p;
-  ci.lext = (const gr_local_input*)e->d_lext.p;
-  ci.n_msgs = nm;
-  ci.n_ext = nx;
-  ci.n_loc = nlc;
-  ci.n_lext = nlx;
+  if ((r = e->d_msgs.grow((size_t)nm * sizeof(gr_cmsg) + 1))) return r;
+  if ((r = e->d_locals.grow((size_t)nlc * sizeof(gr_clocal) + 1))) return r;
+  if ((r = e->d_ext.grow((size_t)nx * sizeof(gr_message) + 1))) return r;
+  if ((r = e->d_lext.grow((size_t)nlx * sizeof(gr_local_input) + 1))) return r;
   if (nm) HIPCHK(hipMemcpyAsync(e->d_msgs.p, in->msgs, (size_t)nm * sizeof(gr_cmsg), hipMemcpyHostToDevice, s));
   if (nlc) HIPCHK(hipMemcpyAsync(e->d_locals.p, in->locals, (size_t)nlc * sizeof(gr_clocal), hipMemcpyHostToDevice, s));
   if (nx) HIPCHK(hipMemcpyAsync(e->d_ext.p, in->ext_msgs, (size_t)nx * sizeof(gr_message), hipMemcpyHostToDevice, s));
   if (nlx)
     HIPCHK(hipMemcpyAsync(e->d_lext.p, in->ext_locals, (size_t)nlx * sizeof(gr_local_input), hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemsetAsync(mark, 0, (size_t)cap * 4, s));
-  HIPCHK(hipMemsetAsync(scal, 0, 16, s));
-  if (e->quiesce && nlc + nlx) {  // as gr_step: no QuiescedTick counts with the manager on the device
-    hipLaunchKernelGGL(io::check_raw_ticks_c, dim3(io_grid(nlc + nlx)), blk, 0, s, ci.loc, nlc, ci.lext, nlx, scal + 1);
-    HIPCHK(hipGetLastError());
-  }
-  hipLaunchKernelGGL(io::mark_inputs_c, dim3(io_grid(nm + nlc)), blk, 0, s, ci, S, cap, mark, scal + 1,
-                     (uint32_t)e->config_entries);
-  HIPCHK(hipGetLastError());
-  if ((r = io_scan(e, mark, lop, cap, s))) return r;
-  hipLaunchKernelGGL(io::finish_lanes, dim3(1), dim3(64), 0, s, (const uint32_t*)mark, (const uint32_t*)lop, cap,
-                     (const uint32_t*)(scal + 1), scal);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(e->h_scal, scal, 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
+  uint32_t nl, err;
+  if ((r = stage_lanes(e, CompactInbox(e, nm, nlc, nx, nlx), &nl, &err))) return r;
   clk.mark("upload+lanes");
-  const uint32_t nl = ((uint32_t*)e->h_scal)[0];
-  if (((uint32_t*)e->h_scal)[1]) return GR_EINVAL;  // nothing of the pass ran
+  if (err) return GR_EINVAL;  // nothing of the pass ran
   e->cpend.on = true;
   e->pending.store(true, std::memory_order_release);
   e->cpend.nm = nm;
@@ -1788,73 +1672,11 @@ static int compact_end_locked(gr_engine* e, gr_coutbox* out, const gr_wire_out_c
   } clear_pending{e->pending};
   memset(out, 0, sizeof(*out));
   PhaseClock clk;
-  const uint32_t S = e->S, cap = e->cfg.max_peers;
-  const uint32_t nm = pend.nm, nlc = pend.nlc, nx = pend.nx, nlx = pend.nlx, nl = pend.nl;
-  if (nl == 0) return GR_OK;
-  const hipStream_t s = e->stream;
-  const dim3 blk(io::kIoBlock);
+  if (pend.nl == 0) return GR_OK;
+  SpaceView vout;
   int r;
-  uint32_t* mark = (uint32_t*)e->d_mark.p;
-  uint32_t* lop = (uint32_t*)e->d_lop.p;
-  uint32_t* scal = (uint32_t*)e->d_scal.p;
-  io::CInbox ci;
-  ci.msgs = (const gr_cmsg*)e->d_msgs.p;
-  ci.ext = (const gr_message*)e->d_ext.p;
-  ci.loc = (const gr_clocal*)e->d_locals.p;
-  ci.lext = (const gr_local_input*)e->d_lext.p;
-  ci.n_msgs = nm;
-  ci.n_ext = nx;
-  ci.n_loc = nlc;
-  ci.n_lext = nlx;
-  (void)nlx;
-  uint32_t* peer_of_lane = e->ln.u32(LR_LANE_PEER);
-  hipLaunchKernelGGL(io::lane_peers, dim3(io_grid(cap)), blk, 0, s, (const uint32_t*)mark, (const uint32_t*)lop, cap,
-                     peer_of_lane);
-  HIPCHK(hipGetLastError());
-  // ---- mailboxes
-  const uint32_t positions = nl * S;
-  const size_t space = gr_space_bytes(1, positions, GR_C);
-  if ((r = grow_device(&e->d_in.p, &e->d_in.n, space))) return r;
-  if ((r = grow_device(&e->d_out.p, &e->d_out.n, space))) return r;
-  const SpaceView vin = make_view(e->d_in.p, 1, positions), vout = make_view(e->d_out.p, 1, positions);
-  hipLaunchKernelGGL(io::clear_counts, dim3(io_grid(vin.pc)), blk, 0, s, vin, vin.pc);  // the count bytes
-  HIPCHK(hipGetLastError());
-  if (nm) {
-    for (gr_engine::Buf* b : {&e->d_keys, &e->d_idx, &e->d_skeys, &e->d_sidx})
-      if ((r = grow_device(&b->p, &b->n, (size_t)nm * 4))) return r;
-    hipLaunchKernelGGL(io::msg_keys_c, dim3(io_grid(nm)), blk, 0, s, ci.msgs, nm, (const uint32_t*)lop, nl,
-                       (uint32_t*)e->d_keys.p, (uint32_t*)e->d_idx.p);
-    HIPCHK(hipGetLastError());
-    if ((r = sort_keys(e, nm, positions, s))) return r;
-    hipLaunchKernelGGL(io::encode_sorted_c, dim3(io_grid(nm)), blk, 0, s, ci, (const uint32_t*)e->d_skeys.p,
-                       (const uint32_t*)e->d_sidx.p, vin, (uint32_t)e->config_entries);
-    HIPCHK(hipGetLastError());
-  }
-  // ---- locals -> lane rows
-  if ((r = grow_device(&e->d_win.p, &e->d_win.n, (size_t)nl * 4))) return r;
-  HIPCHK(hipMemsetAsync(e->d_win.p, 0, (size_t)nl * 4, s));
-  if (nlc) {
-    hipLaunchKernelGGL(io::local_winner_c, dim3(io_grid(nlc)), blk, 0, s, ci.loc, nlc, (const uint32_t*)lop,
-                       (uint32_t*)e->d_win.p);
-    HIPCHK(hipGetLastError());
-  }
-  hipLaunchKernelGGL(io::fill_locals_c, dim3(io_grid(nl)), blk, 0, s, ci, (const uint32_t*)e->d_win.p, nl, e->ln);
-  HIPCHK(hipGetLastError());
-  // ---- the pass
-  StepParams kp = base_params(e);
-  kp.has_locals = 1;
-  kp.has_lane_peer = 1;
-  kp.route_mode = RT_IDENTITY;
-  kp.in = vin;
-  kp.out = vout;
-  kp.n_lanes = nl;
-  kp.qraw = e->ln.u32(LR_TICKS);  // this pass's rows are the raw input: the quiesce pass rewrites them in place
-  HIPCHK(launch_slots(S, kp, e->bail, e->counters, e->cap, (uint32_t)e->launches++, s, next_timing(e)));
-  e->passes++;
-  e->locals_set = false;
-  e->routes_bound = false;
-  if ((r = pack_out_compact(e, nl, vout, out, &clk, wcfg, wout))) return r;
-  return GR_OK;
+  if ((r = run_staged_pass(e, CompactInbox(e, pend.nm, pend.nlc, pend.nx, pend.nlx), pend.nl, &vout))) return r;
+  return pack_out_compact(e, pend.nl, vout, out, &clk, wcfg, wout);
 }
 
 int gr_step_compact(gr_engine* e, const gr_cinbox* in, gr_coutbox* out) {
@@ -1891,17 +1713,17 @@ int gr_cinbox_reserve(gr_engine* e, size_t n_msgs, size_t n_ext_msgs, size_t n_l
     return GR_EINVAL;
   std::lock_guard<std::mutex> guard(e->mu);
   int r;
-  if ((r = grow_pinned(&e->h_inmsgs, &e->h_inmsgs_bytes, n_msgs * sizeof(gr_cmsg) + 1, kInboxPinned))) return r;
-  if ((r = grow_pinned(&e->h_inlocals, &e->h_inlocals_bytes, n_locals * sizeof(gr_clocal) + 1, kInboxPinned))) return r;
-  if ((r = grow_pinned(&e->h_inext, &e->h_inext_bytes, n_ext_msgs * sizeof(gr_message) + 1, kInboxPinned))) return r;
-  if ((r = grow_pinned(&e->h_inlext, &e->h_inlext_bytes, n_ext_locals * sizeof(gr_local_input) + 1, kInboxPinned))) return r;
-  in->msgs = (const gr_cmsg*)e->h_inmsgs;
+  if ((r = e->h_inmsgs.grow(n_msgs * sizeof(gr_cmsg) + 1))) return r;
+  if ((r = e->h_inlocals.grow(n_locals * sizeof(gr_clocal) + 1))) return r;
+  if ((r = e->h_inext.grow(n_ext_msgs * sizeof(gr_message) + 1))) return r;
+  if ((r = e->h_inlext.grow(n_ext_locals * sizeof(gr_local_input) + 1))) return r;
+  in->msgs = (const gr_cmsg*)e->h_inmsgs.p;
   in->n_msgs = n_msgs;
-  in->ext_msgs = (const gr_message*)e->h_inext;
+  in->ext_msgs = (const gr_message*)e->h_inext.p;
   in->n_ext_msgs = n_ext_msgs;
-  in->locals = (const gr_clocal*)e->h_inlocals;
+  in->locals = (const gr_clocal*)e->h_inlocals.p;
   in->n_locals = n_locals;
-  in->ext_locals = (const gr_local_input*)e->h_inlext;
+  in->ext_locals = (const gr_local_input*)e->h_inlext.p;
   in->n_ext_locals = n_ext_locals;
   return GR_OK;
 }
@@ -1977,11 +1799,11 @@ int gr_inbox_reserve(gr_engine* e, size_t n_msgs, size_t n_locals, gr_inbox* in)
   if (!e || !in || n_msgs + n_locals >= 0x80000000ull) return GR_EINVAL;
   std::lock_guard<std::mutex> guard(e->mu);
   int r;
-  if ((r = grow_pinned(&e->h_inmsgs, &e->h_inmsgs_bytes, n_msgs * sizeof(gr_message) + 1, kInboxPinned))) return r;
-  if ((r = grow_pinned(&e->h_inlocals, &e->h_inlocals_bytes, n_locals * sizeof(gr_local_input) + 1, kInboxPinned))) return r;
-  in->msgs = (const gr_message*)e->h_inmsgs;
+  if ((r = e->h_inmsgs.grow(n_msgs * sizeof(gr_message) + 1))) return r;
+  if ((r = e->h_inlocals.grow(n_locals * sizeof(gr_local_input) + 1))) return r;
+  in->msgs = (const gr_message*)e->h_inmsgs.p;
   in->n_msgs = n_msgs;
-  in->locals = (const gr_local_input*)e->h_inlocals;
+  in->locals = (const gr_local_input*)e->h_inlocals.p;
   in->n_locals = n_locals;
   return GR_OK;
 }
@@ -2113,8 +1935,8 @@ int gr_set_locals(gr_engine* e, const gr_local_input* locals, size_t n) {
   HIPCHK(hipDeviceSynchronize());  // a pass in flight on another stream may read the rows
   const hipStream_t s = e->stream;
   int r;
-  if ((r = grow_device(&e->d_locals.p, &e->d_locals.n, n * sizeof(gr_local_input) + 1))) return r;
-  if ((r = grow_device(&e->d_win.p, &e->d_win.n, (size_t)cap * 4))) return r;
+  if ((r = e->d_locals.grow(n * sizeof(gr_local_input) + 1))) return r;
+  if ((r = e->d_win.grow((size_t)cap * 4))) return r;
   if (n) HIPCHK(hipMemcpyAsync(e->d_locals.p, locals, n * sizeof(gr_local_input), hipMemcpyHostToDevice, s));
   HIPCHK(hipMemsetAsync(e->d_win.p, 0, (size_t)cap * 4, s));
   const gr_local_input* dloc = (const gr_local_input*)e->d_locals.p;
@@ -2271,7 +2093,7 @@ int gr_collect_results(gr_engine* e, uint32_t first, gr_peer_result* out, size_t
   HIPCHK(hipDeviceSynchronize());
   const size_t bytes = n * sizeof(gr_peer_result);
   int r;
-  if ((r = grow_device(&e->d_results.p, &e->d_results.n, bytes))) return r;
+  if ((r = e->d_results.grow(bytes))) return r;
   hipLaunchKernelGGL(io::pack_results, dim3(io_grid(n)), dim3(io::kIoBlock), 0, e->stream, e->ln, e->st,
                      (const uint32_t*)nullptr, first, (uint32_t)n, (gr_peer_result*)e->d_results.p);
   HIPCHK(hipGetLastError());
@@ -2280,34 +2102,22 @@ int gr_collect_results(gr_engine* e, uint32_t first, gr_peer_result* out, size_t
   return GR_OK;
 }
 
-int gr_set_elections(gr_engine* e, int on) {
+// A plain run-time switch of the engine (StepParams reads it at the next pass).
+static int set_switch(gr_engine* e, uint8_t gr_engine::*field, int on) {
   if (!e) return GR_EINVAL;
   std::lock_guard<std::mutex> guard(e->mu);
   GR_REFUSE_PENDING(e);
-  e->elections = on ? 1 : 0;
+  e->*field = on ? 1 : 0;
   return GR_OK;
 }
 
+int gr_set_elections(gr_engine* e, int on) { return set_switch(e, &gr_engine::elections, on); }
 int gr_get_elections(const gr_engine* e) { return e ? (int)e->elections : GR_EINVAL; }
 
-int gr_set_snapshots(gr_engine* e, int on) {
-  if (!e) return GR_EINVAL;
-  std::lock_guard<std::mutex> guard(e->mu);
-  GR_REFUSE_PENDING(e);
-  e->snapshots = on ? 1 : 0;
-  return GR_OK;
-}
-
+int gr_set_snapshots(gr_engine* e, int on) { return set_switch(e, &gr_engine::snapshots, on); }
 int gr_get_snapshots(const gr_engine* e) { return e ? (int)e->snapshots : GR_EINVAL; }
 
-int gr_set_config_entries(gr_engine* e, int on) {
-  if (!e) return GR_EINVAL;
-  std::lock_guard<std::mutex> guard(e->mu);
-  GR_REFUSE_PENDING(e);
-  e->config_entries = on ? 1 : 0;
-  return GR_OK;
-}
-
+int gr_set_config_entries(gr_engine* e, int on) { return set_switch(e, &gr_engine::config_entries, on); }
 int gr_get_config_entries(const gr_engine* e) { return e ? (int)e->config_entries : GR_EINVAL; }
 
 int gr_set_quiesce(gr_engine* e, int on) {
@@ -2347,16 +2157,11 @@ static int transfer_quiesce(gr_engine* e, const uint32_t* slots, uint32_t first,
   const size_t bytes = n * sizeof(gr_quiesce_state);
   int r;
   if ((r = ensure_quiesce(e))) return r;
-  if ((r = grow_device(&e->d_peers.p, &e->d_peers.n, bytes))) return r;
-  if ((r = grow_device(&e->d_mark.p, &e->d_mark.n, (size_t)cap * 4))) return r;
-  if ((r = grow_device(&e->d_scal.p, &e->d_scal.n, 16))) return r;
-  if ((r = grow_pinned(&e->h_scal, &e->h_scal_bytes, 16))) return r;
+  if ((r = e->d_peers.grow(bytes))) return r;
+  if ((r = e->d_mark.grow((size_t)cap * 4))) return r;
+  if ((r = ensure_scal(e))) return r;
   const uint32_t* dslots = nullptr;
-  if (slots) {
-    if ((r = grow_device(&e->d_slots.p, &e->d_slots.n, n * 4))) return r;
-    HIPCHK(hipMemcpyAsync(e->d_slots.p, slots, n * 4, hipMemcpyHostToDevice, s));
-    dslots = (const uint32_t*)e->d_slots.p;
-  }
+  if (slots && (r = upload_slots(e, slots, n, &dslots))) return r;
   gr_quiesce_state* dq = (gr_quiesce_state*)e->d_peers.p;
   const dim3 grid(io_grid(n)), blk(io::kIoBlock);
   if (to_device) HIPCHK(hipMemcpyAsync(dq, host, bytes, hipMemcpyHostToDevice, s));
@@ -2366,9 +2171,9 @@ static int transfer_quiesce(gr_engine* e, const uint32_t* slots, uint32_t first,
     hipLaunchKernelGGL(io::check_quiesce, grid, blk, 0, s, to_device ? (const gr_quiesce_state*)dq : nullptr, dslots,
                        (uint32_t)n, cap, (uint32_t*)e->d_mark.p, (uint32_t*)e->d_scal.p);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(e->h_scal, e->d_scal.p, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(e->h_scal.p, e->d_scal.p, 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    const uint32_t err = *(uint32_t*)e->h_scal;
+    const uint32_t err = *(uint32_t*)e->h_scal.p;
     if (err & 2u) return GR_ERANGE;
     if (err & 1u) return GR_EINVAL;
   }
@@ -2418,126 +2223,61 @@ int gr_tick_all(gr_engine* e, uint32_t ticks, uint64_t rand_seed) {
 
 uint64_t gr_splitmix64(uint64_t x) { return q_splitmix64(x); }
 
-int gr_promotions(gr_engine* e, gr_promotion* out, size_t cap, size_t* n) {
+// Drain a device list (a kPromoHeader header of count and overflow flag, then
+// cap_records records): all of it or, without room, nothing and the count.
+static int drain_list(gr_engine* e, uint8_t* base, size_t record_size, size_t cap_records, void* out, size_t cap,
+                      size_t* n) {
   if (!e || !n || (cap && !out)) return GR_EINVAL;
   *n = 0;
   std::lock_guard<std::mutex> guard(e->mu);
   GR_REFUSE_PENDING(e);
   HIPCHK(hipDeviceSynchronize());  // passes may run on the caller's streams (gr_step_device, graph replays)
   uint32_t hdr[2] = {0, 0};
-  HIPCHK(hipMemcpy(hdr, e->promo, sizeof(hdr), hipMemcpyDeviceToHost));
-  const size_t have = std::min<size_t>(hdr[0], e->cfg.max_peers);
+  HIPCHK(hipMemcpy(hdr, base, sizeof(hdr), hipMemcpyDeviceToHost));
+  const size_t have = std::min<size_t>(hdr[0], cap_records);
   if (have > cap) {  // nothing drained: the caller comes back with room
     *n = have;
     return GR_ECAPACITY;
   }
-  if (have) HIPCHK(hipMemcpy(out, e->promo + kPromoHeader, have * sizeof(gr_promotion), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemset(e->promo, 0, 4));  // the count; the overflow flag stays
+  if (have) HIPCHK(hipMemcpy(out, base + kPromoHeader, have * record_size, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemset(base, 0, 4));  // the count; the overflow flag stays
   *n = have;
   return hdr[1] ? GR_ECAPACITY : GR_OK;
 }
 
-// The restored list, drained as gr_promotions drains its own.
+int gr_promotions(gr_engine* e, gr_promotion* out, size_t cap, size_t* n) {
+  return drain_list(e, e ? e->promo : nullptr, sizeof(gr_promotion), e ? e->cfg.max_peers : 0, out, cap, n);
+}
+
 int gr_restored_snapshots(gr_engine* e, gr_restored* out, size_t cap, size_t* n) {
-  if (!e || !n || (cap && !out)) return GR_EINVAL;
-  *n = 0;
-  std::lock_guard<std::mutex> guard(e->mu);
-  GR_REFUSE_PENDING(e);
-  HIPCHK(hipDeviceSynchronize());  // passes may run on the caller's streams (gr_step_device, graph replays)
-  uint32_t hdr[2] = {0, 0};
-  HIPCHK(hipMemcpy(hdr, e->rest, sizeof(hdr), hipMemcpyDeviceToHost));
-  const size_t have = std::min<size_t>(hdr[0], (size_t)kRestStage * e->cfg.max_peers);
-  if (have > cap) {  // nothing drained: the caller comes back with room
-    *n = have;
-    return GR_ECAPACITY;
-  }
-  if (have) HIPCHK(hipMemcpy(out, e->rest + kPromoHeader, have * sizeof(gr_restored), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemset(e->rest, 0, 4));  // the count; the overflow flag stays
-  *n = have;
-  return hdr[1] ? GR_ECAPACITY : GR_OK;
+  return drain_list(e, e ? e->rest : nullptr, sizeof(gr_restored), e ? (size_t)kRestStage * e->cfg.max_peers : 0, out,
+                    cap, n);
 }
 
 #ifdef GR_COVERAGE
-// Coverage build only (libgpuraft_cover.so): per-branch hit counts (gr_cover.h).
-int gr_coverage_read(uint64_t* out, uint32_t n) {
-  if (!out || n < CV_N) return GR_EINVAL;
+// Coverage build only (libgpuraft_cover.so): the per-branch hit counts of one
+// table (gr_cover.h), summed over the kernel translation units: each keeps its own counters.
+static int coverage_read(uint32_t table, uint64_t* out, uint32_t n) {
+  const uint32_t len = cover_len(table);
+  if (!out || n < len) return GR_EINVAL;
   HIPCHK(hipDeviceSynchronize());
-  for (uint32_t k = 0; k < CV_N; ++k) out[k] = 0;
-  HIPCHK(cover_read<1>(out));  // every kernel translation unit keeps its own counters
-  HIPCHK(cover_read<3>(out));
-  HIPCHK(cover_read<5>(out));
-  HIPCHK(cover_read<8>(out));
-  return (int)CV_N;
+  for (uint32_t k = 0; k < len; ++k) out[k] = 0;
+  for (uint32_t S : {1u, 3u, 5u, 8u})
+    HIPCHK(with_slots(S, [&](auto ss) { return cover_read<decltype(ss)::value>(table, out); }));
+  return (int)len;
 }
-const char* gr_coverage_names() {
 #define GR_COVER_NAME(x) #x ","
-  return GR_COVER_IDS(GR_COVER_NAME);
+int gr_coverage_read(uint64_t* out, uint32_t n) { return coverage_read(COVER_STEP, out, n); }
+const char* gr_coverage_names() { return GR_COVER_IDS(GR_COVER_NAME); }
+int gr_coverage_elect_read(uint64_t* out, uint32_t n) { return coverage_read(COVER_ELECT, out, n); }
+const char* gr_coverage_elect_names() { return GR_COVER_ELECT_IDS(GR_COVER_NAME); }
+int gr_coverage_quiesce_read(uint64_t* out, uint32_t n) { return coverage_read(COVER_QUIESCE, out, n); }
+const char* gr_coverage_quiesce_names() { return GR_COVER_QUIESCE_IDS(GR_COVER_NAME); }
+int gr_coverage_snap_read(uint64_t* out, uint32_t n) { return coverage_read(COVER_SNAP, out, n); }
+const char* gr_coverage_snap_names() { return GR_COVER_SNAP_IDS(GR_COVER_NAME); }
+int gr_coverage_cc_read(uint64_t* out, uint32_t n) { return coverage_read(COVER_CC, out, n); }
+const char* gr_coverage_cc_names() { return GR_COVER_CC_IDS(GR_COVER_NAME); }
 #undef GR_COVER_NAME
-}
-// The election handlers' table (gr_cover.h GR_COVER_ELECT_IDS), read the same way.
-int gr_coverage_elect_read(uint64_t* out, uint32_t n) {
-  if (!out || n < CE_N) return GR_EINVAL;
-  HIPCHK(hipDeviceSynchronize());
-  for (uint32_t k = 0; k < CE_N; ++k) out[k] = 0;
-  HIPCHK(cover_elect_read<1>(out));
-  HIPCHK(cover_elect_read<3>(out));
-  HIPCHK(cover_elect_read<5>(out));
-  HIPCHK(cover_elect_read<8>(out));
-  return (int)CE_N;
-}
-const char* gr_coverage_elect_names() {
-#define GR_COVER_NAME(x) #x ","
-  return GR_COVER_ELECT_IDS(GR_COVER_NAME);
-#undef GR_COVER_NAME
-}
-// The quiesce pass's table (gr_cover.h GR_COVER_QUIESCE_IDS), read the same way.
-int gr_coverage_quiesce_read(uint64_t* out, uint32_t n) {
-  if (!out || n < CQ_N) return GR_EINVAL;
-  HIPCHK(hipDeviceSynchronize());
-  for (uint32_t k = 0; k < CQ_N; ++k) out[k] = 0;
-  HIPCHK(cover_quiesce_read<1>(out));
-  HIPCHK(cover_quiesce_read<3>(out));
-  HIPCHK(cover_quiesce_read<5>(out));
-  HIPCHK(cover_quiesce_read<8>(out));
-  return (int)CQ_N;
-}
-const char* gr_coverage_quiesce_names() {
-#define GR_COVER_NAME(x) #x ","
-  return GR_COVER_QUIESCE_IDS(GR_COVER_NAME);
-#undef GR_COVER_NAME
-}
-// The snapshot handlers' table (gr_cover.h GR_COVER_SNAP_IDS), read the same way.
-int gr_coverage_snap_read(uint64_t* out, uint32_t n) {
-  if (!out || n < CS_N) return GR_EINVAL;
-  HIPCHK(hipDeviceSynchronize());
-  for (uint32_t k = 0; k < CS_N; ++k) out[k] = 0;
-  HIPCHK(cover_snap_read<1>(out));
-  HIPCHK(cover_snap_read<3>(out));
-  HIPCHK(cover_snap_read<5>(out));
-  HIPCHK(cover_snap_read<8>(out));
-  return (int)CS_N;
-}
-const char* gr_coverage_snap_names() {
-#define GR_COVER_NAME(x) #x ","
-  return GR_COVER_SNAP_IDS(GR_COVER_NAME);
-#undef GR_COVER_NAME
-}
-// The config-change-entry handlers' table (gr_cover.h GR_COVER_CC_IDS), read the same way.
-int gr_coverage_cc_read(uint64_t* out, uint32_t n) {
-  if (!out || n < CC_N) return GR_EINVAL;
-  HIPCHK(hipDeviceSynchronize());
-  for (uint32_t k = 0; k < CC_N; ++k) out[k] = 0;
-  HIPCHK(cover_cc_read<1>(out));
-  HIPCHK(cover_cc_read<3>(out));
-  HIPCHK(cover_cc_read<5>(out));
-  HIPCHK(cover_cc_read<8>(out));
-  return (int)CC_N;
-}
-const char* gr_coverage_cc_names() {
-#define GR_COVER_NAME(x) #x ","
-  return GR_COVER_CC_IDS(GR_COVER_NAME);
-#undef GR_COVER_NAME
-}
 #endif
 
 }  // extern "C"

@@ -1154,45 +1154,22 @@ hipError_t launch(const StepParams& kp_in, uint32_t* bail_list, uint32_t* counte
 
 
 #ifdef GR_COVERAGE
-// This translation unit's hit counters (gr_cover.h: one static array per code object).
+// The hit-counter tables of gr_cover.h.
+enum CoverTable : uint32_t { COVER_STEP, COVER_ELECT, COVER_QUIESCE, COVER_SNAP, COVER_CC };
+constexpr uint32_t kCoverLen[] = {CV_N, CE_N, CQ_N, CS_N, CC_N};  // by CoverTable
+constexpr uint32_t cover_len(uint32_t table) { return table <= COVER_CC ? kCoverLen[table] : 0; }
+// Add one table of this translation unit's hit counters to out (gr_cover.h: one
+// static array per code object, so the reader is instantiated once in each).
 template <int S>
-hipError_t cover_read(uint64_t* out) {
-  unsigned long long h[CV_N];
-  const hipError_t e = hipMemcpyFromSymbol(h, HIP_SYMBOL(gr_cover_dev), sizeof(h), 0, hipMemcpyDeviceToHost);
+hipError_t cover_read(uint32_t table, uint64_t* out) {
+  const void* const syms[] = {gr_cover_dev, gr_cover_elect_dev, gr_cover_quiesce_dev, gr_cover_snap_dev,
+                              gr_cover_cc_dev};  // by CoverTable
+  const uint32_t len = cover_len(table);
+  if (!len) return hipErrorInvalidValue;
+  unsigned long long h[CV_N + CE_N + CQ_N + CS_N + CC_N];  // room for the longest
+  const hipError_t e = hipMemcpyFromSymbol(h, syms[table], len * sizeof(h[0]), 0, hipMemcpyDeviceToHost);
   if (e == hipSuccess)
-    for (uint32_t k = 0; k < CV_N; ++k) out[k] += h[k];
-  return e;
-}
-template <int S>
-hipError_t cover_elect_read(uint64_t* out) {
-  unsigned long long h[CE_N];
-  const hipError_t e = hipMemcpyFromSymbol(h, HIP_SYMBOL(gr_cover_elect_dev), sizeof(h), 0, hipMemcpyDeviceToHost);
-  if (e == hipSuccess)
-    for (uint32_t k = 0; k < CE_N; ++k) out[k] += h[k];
-  return e;
-}
-template <int S>
-hipError_t cover_quiesce_read(uint64_t* out) {
-  unsigned long long h[CQ_N];
-  const hipError_t e = hipMemcpyFromSymbol(h, HIP_SYMBOL(gr_cover_quiesce_dev), sizeof(h), 0, hipMemcpyDeviceToHost);
-  if (e == hipSuccess)
-    for (uint32_t k = 0; k < CQ_N; ++k) out[k] += h[k];
-  return e;
-}
-template <int S>
-hipError_t cover_snap_read(uint64_t* out) {
-  unsigned long long h[CS_N];
-  const hipError_t e = hipMemcpyFromSymbol(h, HIP_SYMBOL(gr_cover_snap_dev), sizeof(h), 0, hipMemcpyDeviceToHost);
-  if (e == hipSuccess)
-    for (uint32_t k = 0; k < CS_N; ++k) out[k] += h[k];
-  return e;
-}
-template <int S>
-hipError_t cover_cc_read(uint64_t* out) {
-  unsigned long long h[CC_N];
-  const hipError_t e = hipMemcpyFromSymbol(h, HIP_SYMBOL(gr_cover_cc_dev), sizeof(h), 0, hipMemcpyDeviceToHost);
-  if (e == hipSuccess)
-    for (uint32_t k = 0; k < CC_N; ++k) out[k] += h[k];
+    for (uint32_t k = 0; k < len; ++k) out[k] += h[k];
   return e;
 }
 #endif
@@ -1207,12 +1184,7 @@ hipError_t cover_cc_read(uint64_t* out) {
   GR_INSTANTIATE_COVER(SS)                                                                                    \
   }
 #ifdef GR_COVERAGE
-#define GR_INSTANTIATE_COVER(SS)                       \
-  template hipError_t cover_read<SS>(uint64_t*); \
-  template hipError_t cover_elect_read<SS>(uint64_t*); \
-  template hipError_t cover_quiesce_read<SS>(uint64_t*); \
-  template hipError_t cover_snap_read<SS>(uint64_t*);   \
-  template hipError_t cover_cc_read<SS>(uint64_t*);
+#define GR_INSTANTIATE_COVER(SS) template hipError_t cover_read<SS>(uint32_t, uint64_t*);
 #else
 #define GR_INSTANTIATE_COVER(SS)
 #endif
