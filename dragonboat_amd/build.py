@@ -8,6 +8,8 @@
   their reference side, test-only.
 - libhostlane_cc.so, libhostlane_cc_elect.so: the host lane with config-change entries compiled
   on and their reference side, test-only.
+- libhostlane_all.so: the host lane with elections, snapshots and config-change entries all
+  compiled on and the reference side for that configuration, test-only.
 Outputs stay in-tree (git-ignored) so they travel to the GPU box.
 """
 import os
@@ -39,6 +41,7 @@ HOSTLANE_SNAP_LIB = os.path.join(ROOT, "tests", "_build", "libhostlane_snap.so")
 HOSTLANE_SNAP_ELECT_LIB = os.path.join(ROOT, "tests", "_build", "libhostlane_snap_elect.so")
 HOSTLANE_CC_LIB = os.path.join(ROOT, "tests", "_build", "libhostlane_cc.so")
 HOSTLANE_CC_ELECT_LIB = os.path.join(ROOT, "tests", "_build", "libhostlane_cc_elect.so")
+HOSTLANE_ALL_LIB = os.path.join(ROOT, "tests", "_build", "libhostlane_all.so")
 WIRE_SRC = os.path.join(ROOT, "dragonboat_amd", "csrc", "gr_wire.hip")
 WIRE_DEPS = [WIRE_SRC, os.path.join(ROOT, "include", "gpuraft_wire.h"), os.path.join(ROOT, "include", "gpuraft.h"),
              os.path.join(CSRC, "gr_scan.h")]
@@ -319,18 +322,20 @@ def build_config_change_host(force=False):
     return CONFIG_CHANGE_HOST_LIB
 
 
-def build_hostlane_snap(force=False, out=HOSTLANE_SNAP_LIB, extra=()):
-    """libhostlane_snap.so: the host lane with snapshots compiled on
-    (tests/native/hostlane_snap.hip, -DGR_SNAPSHOTS_FORCE=1: its harness zeroes
-    StepParams, so the run-time switch cannot reach it) and the reference side
-    (tests/native/snapshot_ref.cpp, the oracle's raft object driven through its
-    own build_peer / export_peer), for tests/test_snapshots.py."""
+def _hostlane_with_ref(out, src, ref, macros, force, extra_deps=()):
+    """A host-lane build (tests/native/<src>, hipcc host-only with -DGR_COVERAGE
+    and `macros`) linked with its reference side (tests/native/<ref>, g++ over
+    oracle/batch.cpp and tests/native/ref_pass.h) into `out`."""
     os.makedirs(os.path.dirname(out), exist_ok=True)
     odir = os.path.join(ROOT, "oracle")
-    src = os.path.join(ROOT, "tests", "native", "hostlane_snap.hip")
-    ref = os.path.join(ROOT, "tests", "native", "snapshot_ref.cpp")
-    deps = ENGINE_DEPS + [src, ref, os.path.join(ROOT, "tests", "native", "hostlane.hip"),
-                          os.path.join(odir, "batch.cpp"), os.path.join(odir, "raft_oracle.hpp")]
+    native = os.path.join(ROOT, "tests", "native")
+    src, ref = os.path.join(native, src), os.path.join(native, ref)
+    deps = ENGINE_DEPS + [src, ref, os.path.join(native, "hostlane.hip"),
+                          os.path.join(odir, "batch.cpp"), os.path.join(odir, "raft_oracle.hpp")] + \
+        [os.path.join(native, d) for d in extra_deps]
+    with open(ref, encoding="utf-8") as fh:  # the shared pass header, where the reference side includes it
+        if '#include "ref_pass.h"' in fh.read():
+            deps.append(os.path.join(native, "ref_pass.h"))
     if not (force or _stale(out, deps)):
         return out
     with _locked(out):
@@ -339,12 +344,21 @@ def build_hostlane_snap(force=False, out=HOSTLANE_SNAP_LIB, extra=()):
             objs = [out + ".host.o", out + ".ref.o"]
             with ThreadPoolExecutor(2) as ex:
                 fs = [ex.submit(_run, [HIPCC, "--cuda-host-only", "-O2", "-g", "-std=c++17", "-fPIC", "-DGR_COVERAGE",
-                                       "-DGR_SNAPSHOTS_FORCE=1", *extra, *inc, "-c", src, "-o", objs[0]]),
+                                       *macros, *inc, "-c", src, "-o", objs[0]]),
                       ex.submit(_run, ["g++", "-std=c++17", "-O2", "-g", "-fPIC", *inc, "-c", ref, "-o", objs[1]])]
                 for f in fs:
                     f.result()
             _run([HIPCC, "-shared", "-fPIC", *objs, "-o", out, "-lpthread"])
     return out
+
+
+def build_hostlane_snap(force=False, out=HOSTLANE_SNAP_LIB, extra=()):
+    """libhostlane_snap.so: the host lane with snapshots compiled on
+    (tests/native/hostlane_snap.hip, -DGR_SNAPSHOTS_FORCE=1: its harness zeroes
+    StepParams, so the run-time switch cannot reach it) and the reference side
+    (tests/native/snapshot_ref.cpp, the oracle's raft object driven through its
+    own build_peer / export_peer), for tests/test_snapshots.py."""
+    return _hostlane_with_ref(out, "hostlane_snap.hip", "snapshot_ref.cpp", ("-DGR_SNAPSHOTS_FORCE=1", *extra), force)
 
 
 def build_hostlane_snap_elect(force=False):
@@ -359,32 +373,35 @@ def build_hostlane_cc(force=False, out=HOSTLANE_CC_LIB, extra=()):
     StepParams, so the run-time switch cannot reach it) and the reference side
     (tests/native/config_entries_ref.cpp, the oracle's raft object with typed
     in-memory entries), for tests/test_config_entries.py."""
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    odir = os.path.join(ROOT, "oracle")
-    src = os.path.join(ROOT, "tests", "native", "hostlane_cc.hip")
-    ref = os.path.join(ROOT, "tests", "native", "config_entries_ref.cpp")
-    deps = ENGINE_DEPS + [src, ref, os.path.join(ROOT, "tests", "native", "hostlane.hip"),
-                          os.path.join(odir, "batch.cpp"), os.path.join(odir, "raft_oracle.hpp")]
-    if not (force or _stale(out, deps)):
-        return out
-    with _locked(out):
-        if force or _stale(out, deps):
-            inc = ["-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-I" + odir]
-            objs = [out + ".host.o", out + ".ref.o"]
-            with ThreadPoolExecutor(2) as ex:
-                fs = [ex.submit(_run, [HIPCC, "--cuda-host-only", "-O2", "-g", "-std=c++17", "-fPIC", "-DGR_COVERAGE",
-                                       "-DGR_CONFIG_ENTRIES_FORCE=1", *extra, *inc, "-c", src, "-o", objs[0]]),
-                      ex.submit(_run, ["g++", "-std=c++17", "-O2", "-g", "-fPIC", *inc, "-c", ref, "-o", objs[1]])]
-                for f in fs:
-                    f.result()
-            _run([HIPCC, "-shared", "-fPIC", *objs, "-o", out, "-lpthread"])
-    return out
+    return _hostlane_with_ref(out, "hostlane_cc.hip", "config_entries_ref.cpp",
+                              ("-DGR_CONFIG_ENTRIES_FORCE=1", *extra), force)
 
 
 def build_hostlane_cc_elect(force=False):
     """libhostlane_cc_elect.so: the same with elections compiled on too, for
     promotions over uncommitted entries."""
     return build_hostlane_cc(force, HOSTLANE_CC_ELECT_LIB, ("-DGR_ELECTIONS_FORCE=1",))
+
+
+def build_hostlane_all(force=False):
+    """libhostlane_all.so: the host lane with elections, snapshots and
+    config-change entries all compiled on (tests/native/hostlane_all.hip; the
+    three _FORCE macros) and the reference side that speaks both message
+    conventions over a typed log (tests/native/all_switches_ref.cpp), for
+    tests/test_all_switches.py."""
+    native = os.path.join(ROOT, "tests", "native")
+    own = [os.path.join(native, f) for f in ("hostlane_all.hip", "all_switches_ref.cpp")]
+    if not any(os.path.exists(f) for f in own):
+        # A tests/ tree from before this target (an older suite run against this
+        # engine) has neither of its sources and no test that loads it: nothing to
+        # build, and no stale library left behind. One source without the other
+        # is a broken tree and fails below like any missing source.
+        if os.path.exists(HOSTLANE_ALL_LIB):
+            os.unlink(HOSTLANE_ALL_LIB)
+        return None
+    return _hostlane_with_ref(HOSTLANE_ALL_LIB, "hostlane_all.hip", "all_switches_ref.cpp",
+                              ("-DGR_ELECTIONS_FORCE=1", "-DGR_SNAPSHOTS_FORCE=1", "-DGR_CONFIG_ENTRIES_FORCE=1"), force,
+                              extra_deps=("hostlane_snap.hip",))
 
 
 ORACLE_SAN_LIB = os.path.join(ROOT, "oracle", "_build", "liboracle_san.so")
@@ -489,10 +506,10 @@ def build_tools(force=False):
 
 def build_all(force=False):
     # independent targets side by side (each engine build also compiles its units in parallel)
-    with ThreadPoolExecutor(9) as ex:
+    with ThreadPoolExecutor(10) as ex:
         fs = [ex.submit(f, force) for f in (build_engine, build_engine_cover, build_hostlane, build_hostlane_elect, build_wire,
                                             build_hostlane_snap, build_hostlane_snap_elect,
-                                            build_hostlane_cc, build_hostlane_cc_elect)]
+                                            build_hostlane_cc, build_hostlane_cc_elect, build_hostlane_all)]
         build_oracle(force)
         build_wire_oracle(force)
         build_tools(force)

@@ -975,6 +975,17 @@ struct Lane {
           rt[r] = r == 0 ? st : 0;
         }
         dirty |= D_HI | D_COMMITTED | D_WIN | D_INMEM | D_RESTORE;
+        // The entries above idx are gone and committed is idx: the log holds no
+        // config change above committed, whatever the record named (an index
+        // above idx would still compare as live). Through cc(), so the record
+        // moves with the run that stands; without the arrays there is no record.
+        if (config_entries()) {
+          gr_cc_index* r = cc();
+          if (r) {
+            r->last = 0;
+            r->prev = 0;
+          }
+        }
         stage[nrest].index = idx;
         stage[nrest].term = st;
         nrest++;

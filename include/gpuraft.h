@@ -806,9 +806,14 @@ int gr_restore_remotes(gr_engine* e, const uint32_t* slots, const gr_membership*
  * the device does not clear stale values. Slot rules are gr_set_snapshot_recs':
  * out of range or listed twice is GR_ERANGE before anything is written, a call
  * while a gr_step_compact_begin is pending GR_ESTATE. Nothing but the items below
- * moves the record (not a restore, gr_compact_log, gr_commit_update or
- * gr_apply_config_change: committed only grows, staleness covers them), and it
- * belongs to the run that stands: an item that escalates leaves no trace in it.
+ * and a restore moves the record (not gr_compact_log, gr_commit_update,
+ * gr_restore_remotes or gr_apply_config_change: committed only grows, staleness
+ * covers them). A restore from an InstallSnapshot (with snapshots on too) is the
+ * one place where entries above committed vanish while committed moves: it
+ * discards the log above Snapshot.Index and sets committed to it, so a recorded
+ * index above Snapshot.Index would go on comparing as live; the restore leaves
+ * the record {0, 0}. The record belongs to the run that stands: an item that
+ * escalates leaves no trace in it.
  *
  * Message convention (switch on only): a GR_REPLICATE with reject = 1 carries in
  * hint the highest index of a config-change entry among its entries

@@ -3,7 +3,8 @@
 // and the group's snapshot record become an oracle raft object through the
 // oracle's own build_peer (RunLogDB::snap is what LogReader.Snapshot() returns);
 // the pass's items run through the oracle's Handle / tick / propose in the
-// engine's item order, as ob_step2 runs them; export_peer and to_record give
+// engine's item order, as ob_step2 runs them (ref_pass.h, shared with the other
+// reference sides); export_peer and to_record give
 // the records back. This translation unit includes oracle/batch.cpp to reach
 // those functions; the oracle itself is unchanged. What this file adds is
 // gpuraft.h's message convention: an InstallSnapshot record carries
@@ -11,149 +12,25 @@
 // with reject set names the receiver in Snapshot.Membership.Observers.
 // Linked with hostlane_snap.hip into tests/_build/libhostlane_snap*.so.
 #include "batch.cpp"
+#include "ref_pass.h"
 
 namespace {
 
 // gr_message -> raftpb.Message, an InstallSnapshot by the convention
 Message expand(const OPeer& op, const gr_message& g) {
   Message m = from_record(op, g);
-  if (m.Type != InstallSnapshot) return m;
-  m.snapshot.Index = g.log_index;
-  m.snapshot.Term = g.log_term;
-  if (g.reject) m.snapshot.membership.Observers[op.r->nodeID] = "";
-  m.LogIndex = 0;
-  m.LogTerm = 0;
-  m.Commit = 0;
-  m.Reject = false;
+  if (m.Type == InstallSnapshot) refpass::expand_install(op, g, &m);
   return m;
 }
 
 // raftpb.Message -> gr_message, an InstallSnapshot by the convention
 bool contract(const OPeer& op, uint32_t peer, const Message& m, gr_message* o) {
   const bool ok = to_record(op, peer, m, o);
-  if (m.Type == InstallSnapshot) {
-    o->log_index = m.snapshot.Index;
-    o->log_term = m.snapshot.Term;
-  }
+  if (m.Type == InstallSnapshot) refpass::contract_install(m, o);
   return ok;
 }
 
-// One peer's pass: items below `limit` in the engine's order. Returns the
-// item at which the oracle panicked, or -1.
-struct PassOut {
-  std::vector<gr_message> msgs;
-  std::vector<gr_restored> restored;
-  gr_peer_result res;
-  int panic_item = -1;
-  std::string what;
-};
-
-void run_peer(OPeer& op, uint32_t pi, uint32_t S, const std::vector<const gr_message*>& ms, const gr_local_input* L,
-              uint32_t limit, PassOut* po) {
-  raft& r = *op.r;
-  r.msgs.clear();
-  r.readyToRead.clear();
-  op.appendFrom = 0;
-  op.rand.assign(1, L ? L->rand : 0);
-  op.randNext = 0;
-  memset(&po->res, 0, sizeof(po->res));
-  po->res.peer = pi;
-  uint32_t item = 0;
-  auto flush = [&]() {
-    for (auto& m : r.msgs) {
-      gr_message rec;
-      if (!contract(op, pi, m, &rec)) throw std::runtime_error("message not representable as a gr_message record");
-      po->msgs.push_back(rec);
-    }
-    r.msgs.clear();
-  };
-  try {
-    for (const gr_message* gm : ms) {
-      if (item == limit) break;
-      Message m = expand(op, *gm);
-      const u64 before = r.log->lastIndex();
-      const u64 snap0 = r.log->inmem.snapshot ? r.log->inmem.snapshot->Index : 0;
-      const bool member = op.kinds[gm->slot] != GR_SLOT_EMPTY;
-      if (member || !isResponseMessageType(m.Type)) r.Handle(m);  // Peer.Handle (peer.go:199-209)
-      if (m.Type == InstallSnapshot && r.log->inmem.snapshot && r.log->inmem.snapshot->Index != snap0) {
-        gr_restored rr;
-        memset(&rr, 0, sizeof(rr));
-        rr.peer = pi;
-        rr.index = r.log->inmem.snapshot->Index;
-        rr.term = r.log->inmem.snapshot->Term;
-        po->restored.push_back(rr);
-      }
-      if (m.Type == Propose && r.log->lastIndex() > before) {
-        if (!po->res.propose_first) po->res.propose_first = before + 1;
-        po->res.n_forwarded++;
-        po->res.forwarded_entries += (uint32_t)m.Entries.size();
-      }
-      flush();
-      item++;
-    }
-    if (L && item != limit) {
-      if (L->read_index) {
-        Message m;
-        m.Type = ReadIndex;
-        m.Hint = L->read_ctx_low;
-        m.HintHigh = L->read_ctx_high;
-        r.Handle(m);
-        flush();
-        item++;
-      }
-      for (uint32_t k = 0; k < L->ticks && item != limit; ++k) {
-        r.tick();
-        flush();
-        item++;
-      }
-      if (L->quiesced_ticks && item != limit) {
-        for (uint32_t k = 0; k < L->quiesced_ticks; ++k) r.quiescedTick();
-        item++;
-      }
-      if (L->propose_entries && item != limit) {
-        const u64 before = r.log->lastIndex();
-        std::vector<Entry> es(L->propose_entries);
-        const size_t payload = op.entryUB >= 128 ? (size_t)(op.entryUB - 128) : 0;
-        for (auto& e : es) e.Cmd.assign(payload, 0);
-        if (L->propose_has_config_change) es[0].Type = ConfigChangeEntry;
-        Message m;
-        m.Type = Propose;
-        m.From = r.nodeID;
-        m.Entries = es;
-        r.Handle(m);
-        bool fwd = false;
-        for (auto& x : r.msgs) fwd = fwd || x.Type == Propose;
-        flush();
-        if (r.log->lastIndex() > before) {
-          po->res.propose_result = GR_PROP_APPENDED;
-          if (!po->res.propose_first) po->res.propose_first = before + 1;
-        } else {
-          po->res.propose_result = fwd ? GR_PROP_FORWARDED : GR_PROP_DROPPED;
-        }
-        item++;
-      }
-    }
-  } catch (const std::exception& ex) {
-    po->panic_item = (int)item;
-    po->what = ex.what();
-    r.msgs.clear();
-  }
-  gr_peer_result& res = po->res;
-  res.n_ready = (uint8_t)std::min<size_t>(r.readyToRead.size(), 255);
-  for (size_t q = 0; q < r.readyToRead.size() && q < GR_Q; ++q) {
-    res.ready[q].index = r.readyToRead[q].Index;
-    res.ready[q].ctx_low = r.readyToRead[q].ctx.Low;
-    res.ready[q].ctx_high = r.readyToRead[q].ctx.High;
-  }
-  res.append_from = op.appendFrom;
-  res.committed = r.log->committed;
-  res.last_index = r.log->lastIndex();
-  auto es = r.log->entriesToSave();
-  res.save_from = es.empty() ? 0 : es.front().Index;
-  res.term = r.term;
-  res.vote = r.vote;
-  (void)S;
-}
+using refpass::PassOut;
 
 // node id -> slot, members first, then an empty slot that still carries the id
 uint32_t slot_any(const OPeer& op, u64 id) {
@@ -262,25 +139,13 @@ extern "C" int snr_step(uint32_t slots, uint64_t max_entry_size, gr_peer* peers,
                         gr_restored* restored, size_t restored_cap, size_t* n_restored, int32_t* panic_item) {
   if (!in || !n_out || !n_results || !n_restored || !snap) return GR_EINVAL;
   const uint32_t S = slots;
-  std::vector<std::vector<const gr_message*>> by((size_t)n_peers * S);
-  std::vector<uint8_t> has(n_peers, 0);
-  std::vector<const gr_local_input*> loc(n_peers, nullptr);
-  for (size_t k = 0; k < in->n_msgs; ++k) {
-    const gr_message& m = in->msgs[k];
-    if (m.peer >= n_peers || m.slot >= S) return GR_EINVAL;
-    by[(size_t)m.peer * S + m.slot].push_back(&m);
-    has[m.peer] = 1;
-  }
-  for (size_t k = 0; k < in->n_locals; ++k) {
-    if (in->locals[k].peer >= n_peers) return GR_EINVAL;
-    loc[in->locals[k].peer] = &in->locals[k];
-    has[in->locals[k].peer] = 1;
-  }
+  refpass::Sorted so;
+  if (refpass::sort_inbox(in, S, n_peers, &so)) return GR_EINVAL;
   size_t no = 0, nr = 0, ns = 0;
   int rc = GR_OK;
   for (uint32_t pi = 0; pi < n_peers; ++pi) {
     if (panic_item) panic_item[pi] = -1;
-    if (!has[pi]) continue;
+    if (!so.has[pi]) continue;
     OPeer op;
     PassOut po;
     try {
@@ -290,10 +155,7 @@ extern "C" int snr_step(uint32_t slots, uint64_t max_entry_size, gr_peer* peers,
     }
     op.db->snap.Index = snap[pi].index;
     op.db->snap.Term = snap[pi].term;
-    std::vector<const gr_message*> ms;
-    for (uint32_t j = 0; j < S; ++j)
-      for (const gr_message* m : by[(size_t)pi * S + j]) ms.push_back(m);
-    run_peer(op, pi, S, ms, loc[pi], limits ? limits[pi] : 0xFFFFFFFFu, &po);
+    refpass::run_peer(op, pi, so.of(pi), so.loc[pi], limits ? limits[pi] : 0xFFFFFFFFu, &po, expand, contract);
     if (po.panic_item >= 0) {
       if (panic_item) panic_item[pi] = po.panic_item;
       else rc = GR_ESTATE;
