@@ -118,6 +118,11 @@ assert MEMBERSHIP.itemsize == 80
 # gr_cc_index (gpuraft.h, config-change entries on the device)
 CC_INDEX = np.dtype([("last", u64), ("prev", u64)])
 assert CC_INDEX.itemsize == 16
+# gr_update_state / gr_updates (gpuraft.h, updates out of the device-resident path)
+UPD_MORE_TO_APPLY, UPD_EVERY = 0x1, 0x2
+UPD_NONE, UPD_COMPACT, UPD_EXT = 0, 1, 2
+UPDATE_STATE = np.dtype([("term", u64), ("vote", u64), ("commit", u64)])
+assert UPDATE_STATE.itemsize == 24
 SIZES = {"gr_peer": 664, "gr_message": 80, "gr_local_input": 48, "gr_peer_result": 168,
          "gr_remote": 32, "gr_read_status": 32}
 assert PEER.itemsize == SIZES["gr_peer"], PEER.itemsize
@@ -167,6 +172,17 @@ class WireOut(ctypes.Structure):
     _fields_ = [("d_batches", ctypes.c_void_p), ("n_batches", ctypes.c_size_t),
                 ("d_msgs", ctypes.c_void_p), ("n_msgs", ctypes.c_size_t),
                 ("batch_target", ctypes.c_void_p)]
+
+
+class Updates(ctypes.Structure):
+    _fields_ = [("results", ctypes.c_void_p), ("n_results", ctypes.c_size_t),
+                ("ext_results", ctypes.c_void_p), ("n_ext_results", ctypes.c_size_t)]
+
+
+class UpdatesInfo(ctypes.Structure):
+    _fields_ = [("n_results", ctypes.c_uint64), ("n_ext_results", ctypes.c_uint64), ("bytes_down", ctypes.c_uint64),
+                ("classify_ms", ctypes.c_double), ("pack_ms", ctypes.c_double), ("timed", ctypes.c_uint32),
+                ("pad", ctypes.c_uint32)]
 
 
 class CInbox(ctypes.Structure):
@@ -229,6 +245,7 @@ EXPORTS = [
     "gr_set_config_entries", "gr_get_config_entries", "gr_set_cc_indexes", "gr_get_cc_indexes",
     "gr_set_quiesce", "gr_get_quiesce", "gr_load_quiesce", "gr_sync_quiesce", "gr_load_quiesce_peers",
     "gr_sync_quiesce_peers", "gr_tick_all", "gr_splitmix64",
+    "gr_set_update_states", "gr_get_update_states", "gr_collect_updates", "gr_update_class", "gr_updates_last",
 ]
 
 

@@ -184,6 +184,17 @@ struct gr_engine {
   QuiesceRec* qprev = nullptr;
   uint32_t* qcfg = nullptr;
   uint32_t* qraw = nullptr;
+  // the update states (gr_set_update_states, gr_collect_updates): Peer.prevState,
+  // cap records, allocated zeroed by the first call that uses them
+  gr_update_state* upd_state = nullptr;
+  // the lane rows are in the device-resident form (lane l steps peer l), so
+  // gr_collect_updates may read them: true while they are all zero (gr_create),
+  // set by gr_step_device and gr_graph_replay, cleared by every staged host pass
+  bool lanes_by_slot = true;
+  // gr_updates_last: what the last gr_collect_updates copied down, and, with
+  // per-pass timing on, events around its two kernels (made on first use)
+  hipEvent_t upd_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  gr_updates_info upd_last{};
   std::string wclock_path;
 
   // gr_step buffers (gr_io.h)
@@ -202,6 +213,8 @@ struct gr_engine {
   Buf d_ext, d_lext;        // gr_step_compact: ext message / local records
   Buf d_oc64, d_off64, d_rx, d_roff;  // compact outbox counts and offsets
   Buf d_outext, d_resext;   // compact outbox ext records
+  Buf d_ucls, d_ucnt, d_uoff;  // gr_collect_updates: class bytes, tile counts and their exclusive scan
+  Pinned h_upd, h_updext;      // its records, the caller's until the next gr_collect_updates
   Buf d_nodes;              // gr_bind_nodes: (cluster, node) -> slot table
   Buf d_wrec, d_why, d_unr; // gr_step_wire: routed records, per-message reason, unrouted indices
   uint32_t nodes_cap = 0;
@@ -336,6 +349,22 @@ int ensure_quiesce(gr_engine* e) {
   e->qprev = e->qrec + cap;
   e->qcfg = (uint32_t*)(e->qprev + cap);
   e->qraw = e->qcfg + cap;
+  return GR_OK;
+}
+
+// The update states' allocation (zeroed: the empty State, peer.go:96-100).
+int ensure_update_state(gr_engine* e) {
+  if (e->upd_state) return GR_OK;
+  const size_t bytes = (size_t)e->cap * sizeof(gr_update_state);
+  if (hipMalloc((void**)&e->upd_state, bytes) != hipSuccess) {
+    e->upd_state = nullptr;
+    return GR_ENOMEM;
+  }
+  if (hipMemset(e->upd_state, 0, bytes) != hipSuccess) {
+    (void)hipFree(e->upd_state);
+    e->upd_state = nullptr;
+    return GR_EDEVICE;
+  }
   return GR_OK;
 }
 
@@ -674,6 +703,7 @@ int run_staged_pass(gr_engine* e, const In& in, uint32_t nl, SpaceView* vout) {
   kp.qraw = e->ln.u32(LR_TICKS);  // this pass's rows are the raw input: the quiesce pass rewrites them in place
   HIPCHK(launch_slots(S, kp, e->bail, e->counters, e->cap, (uint32_t)e->launches++, s, next_timing(e)));
   e->passes++;
+  e->lanes_by_slot = false;  // lanes are numbered by input now: gr_collect_updates waits for a device pass
   e->locals_set = false;    // the lane rows now hold this pass's compact locals
   e->routes_bound = false;  // and RT_IDENTITY replaced the bound routes
   return GR_OK;
@@ -810,6 +840,9 @@ void gr_destroy(gr_engine* e) {
   if (e->rest) (void)hipFree(e->rest);
   if (e->cc_rec) (void)hipFree(e->cc_rec);
   if (e->qmem) (void)hipFree(e->qmem);
+  if (e->upd_state) (void)hipFree(e->upd_state);
+  for (hipEvent_t ev : e->upd_ev)
+    if (ev) (void)hipEventDestroy(ev);
   if (e->tail_hint) (void)hipHostFree(e->tail_hint);
   if (e->wclock) {
     std::vector<uint64_t> h(2 * (size_t)kGeneralWaveSlots * kWaveClockWords);
@@ -930,6 +963,26 @@ int gr_get_cc_indexes(gr_engine* e, const uint32_t* slots, gr_cc_index* out, siz
   return slot_list_op(e, slots, out, n, SL_DOWN, nullptr, [e](const SlotArgs<gr_cc_index>& a) {
     hipLaunchKernelGGL(io::get_cc_indexes, a.grid, a.blk, 0, a.s, (const gr_cc_index*)e->cc_rec, a.slots, a.recs,
                        a.n);
+    return GR_OK;
+  });
+}
+
+// The update states of a slot list (gpuraft.h): a side array, as the snapshot
+// records, allocated by the first call.
+int gr_set_update_states(gr_engine* e, const uint32_t* slots, const gr_update_state* recs, size_t n) {
+  return slot_list_op(e, slots, recs, n, SL_UP, nullptr, [e](const SlotArgs<const gr_update_state>& a) -> int {
+    const int r = ensure_update_state(e);
+    if (r) return r;
+    hipLaunchKernelGGL(io::set_update_states, a.grid, a.blk, 0, a.s, e->upd_state, a.slots, a.recs, a.n);
+    return GR_OK;
+  });
+}
+int gr_get_update_states(gr_engine* e, const uint32_t* slots, gr_update_state* out, size_t n) {
+  return slot_list_op(e, slots, out, n, SL_DOWN, nullptr, [e](const SlotArgs<gr_update_state>& a) -> int {
+    const int r = ensure_update_state(e);
+    if (r) return r;
+    hipLaunchKernelGGL(io::get_update_states, a.grid, a.blk, 0, a.s, (const gr_update_state*)e->upd_state, a.slots,
+                       a.recs, a.n);
     return GR_OK;
   });
 }
@@ -2003,8 +2056,10 @@ int gr_step_device(gr_engine* e, const void* in_space, void* out_space, uint32_t
   // (uncontended: one lock per pass)
   std::lock_guard<std::mutex> guard(e->mu);
   GR_REFUSE_PENDING(e);  // the pending compact pass owns the lane rows and bail lists
-  return step_device_locked(e, in_space, out_space, in_chunks, in_positions, out_chunks, out_positions, depth,
-                            n_peers, stream);
+  const int r = step_device_locked(e, in_space, out_space, in_chunks, in_positions, out_chunks, out_positions, depth,
+                                   n_peers, stream);
+  if (r == GR_OK) e->lanes_by_slot = true;
+  return r;
 }
 
 // A captured sequence of device-resident passes (gpuraft.h gr_graph_*).
@@ -2075,6 +2130,7 @@ int gr_graph_replay(gr_graph* g, void* stream) {
   e->launches += g->n_passes;
   e->hint_flip += g->n_passes;
   e->passes += g->n_passes;
+  e->lanes_by_slot = true;
   return GR_OK;
 }
 
@@ -2099,6 +2155,101 @@ int gr_collect_results(gr_engine* e, uint32_t first, gr_peer_result* out, size_t
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(out, e->d_results.p, bytes, hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
+  return GR_OK;
+}
+
+// gpuraft.h gr_update_class: the rule on the host (gr_host.h update_class, which
+// the classify kernel runs too).
+int gr_update_class(const gr_peer_result* r, uint64_t log_applied, uint64_t first_index_m1,
+                    const gr_update_state* prev, uint32_t flags) {
+  if (!r || !prev || (flags & ~(uint32_t)(GR_UPD_MORE_TO_APPLY | GR_UPD_EVERY))) return GR_EINVAL;
+  return update_class(update_fields(*r), log_applied, first_index_m1, *prev, flags);
+}
+
+// Peer.HasUpdate / GetUpdate for slots [first, first + n) after a device-resident
+// pass (gr_io.h update_classify / update_pack): only the reported peers' records
+// cross PCIe.
+int gr_collect_updates(gr_engine* e, uint32_t first, uint32_t n, uint32_t flags, gr_updates* out) {
+  if (!e || !out || (flags & ~(uint32_t)(GR_UPD_MORE_TO_APPLY | GR_UPD_EVERY))) return GR_EINVAL;
+  if ((uint64_t)first + n > e->cfg.max_peers) return GR_EINVAL;
+  std::lock_guard<std::mutex> guard(e->mu);
+  GR_REFUSE_PENDING(e);
+  if (!e->lanes_by_slot) return GR_ESTATE;  // the last pass was a host-path one: lanes are not slots
+  memset(out, 0, sizeof(*out));
+  if (n == 0) return GR_OK;
+  HIPCHK(hipDeviceSynchronize());  // passes may run on the caller's streams
+  const hipStream_t s = e->stream;
+  const uint32_t ntiles = ((first + n - 1) >> GR_TILE_SHIFT) - (first >> GR_TILE_SHIFT) + 1;
+  const dim3 grid(ntiles), blk(io::kIoBlock);
+  int r;
+  if ((r = ensure_update_state(e))) return r;
+  if ((r = ensure_scal(e))) return r;
+  if ((r = e->d_ucls.grow((size_t)ntiles * kTileW))) return r;
+  if ((r = e->d_ucnt.grow((size_t)ntiles * 8))) return r;
+  if ((r = e->d_uoff.grow((size_t)ntiles * 8))) return r;
+  const bool timed = e->timing;
+  if (timed)
+    for (hipEvent_t& ev : e->upd_ev)
+      if (!ev) HIPCHK(hipEventCreate(&ev));
+  uint8_t* cls = e->d_ucls.as<uint8_t>();
+  uint64_t* cnt = e->d_ucnt.as<uint64_t>();
+  uint64_t* off = e->d_uoff.as<uint64_t>();
+  uint32_t* scal = e->d_scal.as<uint32_t>();
+  if (timed) HIPCHK(hipEventRecord(e->upd_ev[0], s));
+  hipLaunchKernelGGL(io::update_classify, grid, blk, 0, s, e->ln, e->st, (const gr_update_state*)e->upd_state, first,
+                     n, flags, cls, cnt);
+  HIPCHK(hipGetLastError());
+  if (timed) HIPCHK(hipEventRecord(e->upd_ev[1], s));
+  if ((r = io_scan64(e, cnt, off, ntiles, s))) return r;
+  hipLaunchKernelGGL(io::update_totals, dim3(1), dim3(64), 0, s, (const uint64_t*)cnt, (const uint64_t*)off, ntiles,
+                     scal);
+  HIPCHK(hipGetLastError());
+  // every device-to-host copy of this call goes through here and is counted
+  gr_updates_info info{};
+  const auto down = [&](void* dst, const void* src, size_t bytes) {
+    info.bytes_down += bytes;
+    return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s);
+  };
+  HIPCHK(down(e->h_scal.p, scal, 8));  // the totals
+  HIPCHK(hipStreamSynchronize(s));
+  const uint32_t nr = e->h_scal.as<uint32_t>()[0], nx = e->h_scal.as<uint32_t>()[1];
+  const size_t rbytes = (size_t)nr * sizeof(gr_cresult), xbytes = (size_t)nx * sizeof(gr_peer_result);
+  if (nr) {  // no record, nothing to pack: no update state moves either
+    if ((r = e->d_results.grow(rbytes))) return r;
+    if ((r = e->d_resext.grow(xbytes + 1))) return r;
+    if ((r = e->h_upd.grow(rbytes))) return r;
+    if ((r = e->h_updext.grow(xbytes + 1))) return r;
+    if (timed) HIPCHK(hipEventRecord(e->upd_ev[2], s));
+    hipLaunchKernelGGL(io::update_pack, grid, blk, 0, s, e->ln, e->st, e->upd_state, first, (const uint8_t*)cls,
+                       (const uint64_t*)off, e->d_results.as<gr_cresult>(), e->d_resext.as<gr_peer_result>());
+    HIPCHK(hipGetLastError());
+    if (timed) HIPCHK(hipEventRecord(e->upd_ev[3], s));
+    HIPCHK(down(e->h_upd.p, e->d_results.p, rbytes));
+    if (nx) HIPCHK(down(e->h_updext.p, e->d_resext.p, xbytes));
+    HIPCHK(hipStreamSynchronize(s));
+  }
+  if (timed) {
+    float a = 0, b = 0;
+    HIPCHK(hipEventElapsedTime(&a, e->upd_ev[0], e->upd_ev[1]));
+    if (nr) HIPCHK(hipEventElapsedTime(&b, e->upd_ev[2], e->upd_ev[3]));
+    info.classify_ms = a;
+    info.pack_ms = b;
+    info.timed = 1;
+  }
+  info.n_results = nr;
+  info.n_ext_results = nx;
+  e->upd_last = info;
+  out->results = nr ? e->h_upd.as<gr_cresult>() : nullptr;
+  out->n_results = nr;
+  out->ext_results = nx ? e->h_updext.as<gr_peer_result>() : nullptr;
+  out->n_ext_results = nx;
+  return GR_OK;
+}
+
+int gr_updates_last(gr_engine* e, gr_updates_info* out) {
+  if (!e || !out) return GR_EINVAL;
+  std::lock_guard<std::mutex> guard(e->mu);
+  *out = e->upd_last;
   return GR_OK;
 }
 

@@ -610,6 +610,12 @@ __host__ __device__ inline bool result_needs_ext(uint8_t rf) {
 }
 // The compact result (gpuraft.h gr_cresult); false when it needs the full
 // record (an escalation, or an index range the relative fields cannot carry).
+// (cresult_fits: the test alone, from the four fields it reads.)
+__host__ __device__ inline bool cresult_fits(uint8_t escalation, uint64_t committed, uint64_t last_index,
+                                             uint64_t save_from) {
+  const uint64_t lag = last_index - committed, save = save_from ? last_index - save_from + 1 : 0;
+  return !escalation && committed <= last_index && !(lag >> 32) && save_from <= last_index + 1 && save <= 0xFFu;
+}
 __host__ __device__ inline bool cresult_of(const gr_peer_result& r, gr_cresult* c) {
   *c = gr_cresult{};
   c->peer = r.peer;
@@ -620,8 +626,62 @@ __host__ __device__ inline bool cresult_of(const gr_peer_result& r, gr_cresult* 
   const uint64_t lag = r.last_index - r.committed, save = r.save_from ? r.last_index - r.save_from + 1 : 0;
   c->commit_lag = (uint32_t)lag;
   c->save_count = (uint8_t)save;
-  return !r.escalation && r.committed <= r.last_index && !(lag >> 32) && r.save_from <= r.last_index + 1 &&
-         save <= 0xFFu;
+  return cresult_fits(r.escalation, r.committed, r.last_index, r.save_from);
+}
+
+// ---- updates out of the device-resident path (gpuraft.h gr_collect_updates)
+// The fields of a result record that Peer.HasUpdate / GetUpdate ask about
+// (peer.go:212-241, 311-337): the classify kernel fills them from a few rows
+// without building the record.
+struct UpdateFields {
+  uint64_t term, vote, committed, last_index, save_from;
+  uint8_t escalation, propose_result, n_ready, n_forwarded;
+};
+__host__ __device__ inline UpdateFields update_fields(const gr_peer_result& r) {
+  return {r.term, r.vote, r.committed, r.last_index, r.save_from, r.escalation, r.propose_result, r.n_ready,
+          r.n_forwarded};
+}
+// gpuraft.h gr_update_class, the one rule host and device share. Reported:
+// State changed (peer.go:220-223), entries to save (:231), entries to apply
+// (:234 with hasEntriesToApply, logentry.go:245-255), ready to read (:237), the
+// engine's own conditions, or GR_UPD_EVERY. Left out on purpose: len(r.msgs) > 0
+// (:228; the messages stay in the out space) and inmem.snapshot (:224; a restore
+// moves committed, so the State condition reports it). EXT: cresult_of's test,
+// ReadyToRead or forwarded batches, or a term / vote that differs from prev
+// (against prev and not the pass's RF_HARDSTATE: a change in a pass nobody
+// collected must still arrive in full).
+__host__ __device__ inline int update_class(const UpdateFields& f, uint64_t log_applied, uint64_t first_index_m1,
+                                            const gr_update_state& prev, uint32_t flags) {
+  const bool nonempty = (f.term | f.vote | f.committed) != 0;  // pb.IsEmptyState
+  const bool hard = f.term != prev.term || f.vote != prev.vote;
+  const bool changed = nonempty && (hard || f.committed != prev.commit);
+  const uint64_t a = log_applied + 1, b = first_index_m1 + 1, first_not_applied = a > b ? a : b;
+  const bool apply = (flags & GR_UPD_MORE_TO_APPLY) && f.committed + 1 > first_not_applied;
+  if (!(changed || f.save_from || apply || f.n_ready || f.escalation || f.propose_result != GR_PROP_NONE ||
+        f.n_forwarded || (flags & GR_UPD_EVERY)))
+    return GR_UPD_NONE;
+  return !cresult_fits(f.escalation, f.committed, f.last_index, f.save_from) || f.n_ready || f.n_forwarded || hard
+             ? GR_UPD_EXT
+             : GR_UPD_COMPACT;
+}
+// The update fields of lane l = peer p after a device-resident pass, from
+// LR_RFLAGS and the lane rows its flags name, the state rows and nothing else
+// (what make_result puts into the same fields). SR_COMMITTED is read only where
+// the header does not carry the lag.
+__host__ __device__ inline UpdateFields lane_update_fields(const LaneBase& L, const StateBase& st, uint32_t p) {
+  UpdateFields f{};
+  const uint8_t rf = L.u8(LR_RFLAGS)[p];
+  if (rf & RF_ESCALATED) f.escalation = L.u8(LR_ESC_REASON)[p];
+  if (rf & RF_PROPOSE) f.propose_result = (rf & RF_PROP_OK) ? (uint8_t)GR_PROP_APPENDED : L.u8(LR_PROP_RESULT)[p];
+  if (rf & RF_READY) f.n_ready = L.u8(LR_RTR_COUNT)[p];
+  if (rf & RF_FORWARDED) f.n_forwarded = L.u8(LR_FWD_COUNT)[p];
+  const uint64_t h = st.u64(SR_HDR)[p];
+  f.last_index = st.u64(SR_LAST_INDEX)[p];
+  f.committed = h_committed(h, f.last_index, h_cl(h) ? 0 : st.u64(SR_COMMITTED)[p]);
+  f.save_from = save_from(st.u64(SR_SAVED_TO)[p], st.u64(SR_MARKER)[p], f.last_index);
+  f.term = st.u64(SR_TERM)[p];
+  f.vote = st.u64(SR_VOTE)[p];
+  return f;
 }
 
 inline uint64_t space_total_bytes(uint32_t n_chunks, uint32_t positions, uint32_t depth = GR_C) {

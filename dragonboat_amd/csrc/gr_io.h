@@ -1650,5 +1650,108 @@ __global__ void get_cc_indexes(const gr_cc_index* recs, const uint32_t* slots, g
   for (uint32_t x = io_tid(); x < n; x += io_stride()) out[x] = recs[slots[x]];
 }
 
+// gr_set_update_states / gr_get_update_states: the side array of update states
+// (Peer.prevState) over a slot list (slots checked on the host: in range, each once).
+__global__ void set_update_states(gr_update_state* recs, const uint32_t* slots, const gr_update_state* in,
+                                  uint32_t n) {
+  for (uint32_t x = io_tid(); x < n; x += io_stride()) recs[slots[x]] = in[x];
+}
+__global__ void get_update_states(const gr_update_state* recs, const uint32_t* slots, gr_update_state* out,
+                                  uint32_t n) {
+  for (uint32_t x = io_tid(); x < n; x += io_stride()) out[x] = recs[slots[x]];
+}
+
+// ---- updates out of the device-resident path (gpuraft.h gr_collect_updates):
+// a stream compaction of the reported peers of slots [first, first + n) that
+// keeps slot order, with no atomics: update_classify (a class byte per slot, one
+// packed count per tile) -> exclusive scan of the tile counts -> update_totals
+// -> update_pack (records at tile offset + wave prefix + rank in the ballot).
+// Workgroup b of both kernels owns state tile (first / kTileW) + b, so every row
+// segment a wave reads is one coalesced block, as in the step kernels; slots of
+// the first and last tile outside the range are masked (class NONE). There lane
+// l steps peer l (the device-resident path).
+static_assert(kIoBlock == (int)kTileW, "one workgroup per state tile");
+constexpr uint32_t kUpdWaves = kIoBlock / 64;
+
+// Exclusive prefix of this wave's packed count among the workgroup's waves, and
+// the workgroup's total: (records << 32 | ext) of each wave through LDS.
+__device__ inline uint64_t upd_wave_prefix(uint64_t wave_cnt, uint64_t* lds, uint64_t* total) {
+  const uint32_t w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) lds[w] = wave_cnt;
+  __syncthreads();
+  uint64_t off = 0, tot = 0;
+#pragma unroll
+  for (uint32_t k = 0; k < kUpdWaves; ++k) {
+    off += k < w ? lds[k] : 0ull;
+    tot += lds[k];
+  }
+  *total = tot;
+  return off;
+}
+
+// cls[b * kTileW + t]: the class of slot (first / kTileW + b) * kTileW + t;
+// cnt[b]: the tile's reported peers (high word) and those that need the full
+// record (low word), as out_counts_c packs its two counts. No gr_peer_result is
+// built here: host::lane_update_fields reads the rows the rule needs.
+__global__ __launch_bounds__(kIoBlock) void update_classify(LaneBase L, StateBase st, const gr_update_state* us,
+                                                            uint32_t first, uint32_t n, uint32_t flags, uint8_t* cls,
+                                                            uint64_t* cnt) {
+  __shared__ uint64_t lds[kUpdWaves];
+  const uint32_t p = ((first >> GR_TILE_SHIFT) + blockIdx.x) * kTileW + threadIdx.x;
+  int c = GR_UPD_NONE;
+  if (p >= first && p - first < n)
+    c = host::update_class(host::lane_update_fields(L, st, p), st.u64(SR_LOG_APPLIED)[p], st.u64(SR_LO)[p], us[p],
+                           flags);
+  cls[(uint64_t)blockIdx.x * kTileW + threadIdx.x] = (uint8_t)c;
+  const uint64_t rep = __ballot(c != GR_UPD_NONE), ext = __ballot(c == GR_UPD_EXT);
+  uint64_t tot;
+  (void)upd_wave_prefix(((uint64_t)__popcll(rep) << 32) | (uint64_t)__popcll(ext), lds, &tot);
+  if (threadIdx.x == 0) cnt[blockIdx.x] = tot;
+}
+
+// totals[0..1] = records, ext records of the whole range (one D2H).
+__global__ void update_totals(const uint64_t* cnt, const uint64_t* off, uint32_t ntiles, uint32_t* totals) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) {
+    const uint64_t t = ntiles ? off[ntiles - 1] + cnt[ntiles - 1] : 0;
+    totals[0] = (uint32_t)(t >> 32);
+    totals[1] = (uint32_t)t;
+  }
+}
+
+// Only reported lanes build their record (host::make_result / cresult_of), write
+// it (and, for GR_UPD_EXT, the full record), store the new update state, the
+// prevState half of Peer.Commit (peer.go:246-248), and clear their result flags.
+// A sparse population touches few rows here.
+__global__ __launch_bounds__(kIoBlock) void update_pack(LaneBase L, StateBase st, gr_update_state* us,
+                                                        uint32_t first, const uint8_t* cls, const uint64_t* off,
+                                                        gr_cresult* rec, gr_peer_result* ext) {
+  __shared__ uint64_t lds[kUpdWaves];
+  const uint32_t p = ((first >> GR_TILE_SHIFT) + blockIdx.x) * kTileW + threadIdx.x;
+  const uint32_t c = cls[(uint64_t)blockIdx.x * kTileW + threadIdx.x];
+  const uint64_t rep = __ballot(c != GR_UPD_NONE), xb = __ballot(c == GR_UPD_EXT);
+  uint64_t tot;
+  const uint64_t base = off[blockIdx.x] +
+                        upd_wave_prefix(((uint64_t)__popcll(rep) << 32) | (uint64_t)__popcll(xb), lds, &tot);
+  if (c == GR_UPD_NONE) return;
+  // rank among the wave's lower lanes (mbcnt)
+  const uint32_t ri = (uint32_t)(base >> 32) + __builtin_amdgcn_mbcnt_hi((uint32_t)(rep >> 32),
+                                                   __builtin_amdgcn_mbcnt_lo((uint32_t)rep, 0u));
+  const gr_peer_result pr = host::make_result(L, st, p, p);
+  gr_cresult cr;
+  (void)host::cresult_of(pr, &cr);
+  if (c == GR_UPD_EXT) {
+    const uint32_t xi = (uint32_t)base + __builtin_amdgcn_mbcnt_hi((uint32_t)(xb >> 32),
+                                             __builtin_amdgcn_mbcnt_lo((uint32_t)xb, 0u));
+    cr.flags = GR_CR_EXT;
+    cr.aux = xi;
+    ext[xi] = pr;
+  }
+  rec[ri] = cr;
+  if (pr.term | pr.vote | pr.committed) us[p] = gr_update_state{pr.term, pr.vote, pr.committed};
+  // the record took the lane's per-pass fields with it (Peer.Commit drops msgs and
+  // readyToRead the same way): a second collect reports only what persists in state
+  L.u8(LR_RFLAGS)[p] = 0;
+}
+
 }  // namespace io
 }  // namespace gr

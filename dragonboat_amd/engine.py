@@ -169,6 +169,12 @@ def load_library(path=LIB_PATH):
                                          c.c_uint32, c.c_void_p, c.c_uint32, c.POINTER(abi.WireOutCfg), c.c_void_p,
                                          c.POINTER(c.c_size_t), c.c_void_p, c.POINTER(c.c_size_t), c.c_void_p,
                                          c.c_void_p]
+    if hasattr(lib, "gr_collect_updates"):  # (older builds loaded for A/B runs lack the updates path)
+        lib.gr_set_update_states.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t]
+        lib.gr_get_update_states.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t]
+        lib.gr_collect_updates.argtypes = [c.c_void_p, c.c_uint32, c.c_uint32, c.c_uint32, c.POINTER(abi.Updates)]
+        lib.gr_update_class.argtypes = [c.c_void_p, c.c_uint64, c.c_uint64, c.c_void_p, c.c_uint32]
+        lib.gr_updates_last.argtypes = [c.c_void_p, c.POINTER(abi.UpdatesInfo)]
     if path == LIB_PATH:
         _lib = lib
     _libs[path] = lib
@@ -230,6 +236,56 @@ def wire_out_host(msgs, cluster_ids, node_ids, remote_ids, target_of, n_targets,
                                 ctypes.byref(c), ptr(bat), ctypes.byref(nb), ptr(wm), ctypes.byref(nw), ptr(bt),
                                 ptr(held)), "gr_wire_out_host")
     return bat[:nb.value].copy(), wm[:nw.value].copy(), bt[:nb.value].copy(), held.astype(bool)
+
+
+def update_class(results, log_applied, first_index_m1, prev, more_to_apply=True, every=False, lib=None):
+    """gr_update_class (the host form of the rule gr_collect_updates runs on the
+    device; no engine, no GPU) for arrays of abi.RESULT records, their peers'
+    log_applied and first_index_m1, and their abi.UPDATE_STATE records. Returns
+    abi.UPD_NONE / UPD_COMPACT / UPD_EXT per record."""
+    lib = lib or load_library()
+    res = np.ascontiguousarray(np.atleast_1d(results), abi.RESULT)
+    prev = np.ascontiguousarray(np.atleast_1d(prev), abi.UPDATE_STATE)
+    la = np.broadcast_to(np.asarray(log_applied, np.uint64), res.shape)
+    lo = np.broadcast_to(np.asarray(first_index_m1, np.uint64), res.shape)
+    assert len(prev) == len(res)
+    flags = (abi.UPD_MORE_TO_APPLY if more_to_apply else 0) | (abi.UPD_EVERY if every else 0)
+    out = np.zeros(len(res), np.int32)
+    rs, ps = abi.RESULT.itemsize, abi.UPDATE_STATE.itemsize
+    for k in range(len(res)):
+        out[k] = lib.gr_update_class(res.ctypes.data + k * rs, int(la[k]), int(lo[k]), prev.ctypes.data + k * ps,
+                                     flags)
+    if np.any(out < 0):
+        _check(int(out.min()), "gr_update_class")
+    return out
+
+
+def expand_updates(cresults, ext, term, vote, propose_entries=None):
+    """What gr_collect_updates returned as abi.RESULT records, by gpuraft.h's
+    gr_cresult rules. term / vote: per engine slot, the host's update states
+    before the collect (a compact record says they did not change; a changed
+    term or vote arrives as an ext record). propose_entries: per engine slot,
+    the bound ProposeEntries counts, which propose_first of a GR_PROP_APPENDED
+    record follows from (omitted: propose_first stays 0). A compact record has no
+    ReadyToRead and no forwarded batches, and does not carry append_from."""
+    cr = np.asarray(cresults, abi.CRESULT)
+    res = np.zeros(len(cr), abi.RESULT)
+    for f in ("peer", "escalation", "propose_result", "last_index"):
+        res[f] = cr[f]
+    res["esc_item"] = cr["aux"]
+    res["committed"] = cr["last_index"] - cr["commit_lag"]
+    sc = cr["save_count"].astype(np.uint64)
+    res["save_from"] = np.where(sc > 0, cr["last_index"] - sc + np.uint64(1), 0)
+    p = cr["peer"].astype(np.int64)
+    res["term"], res["vote"] = np.asarray(term, np.uint64)[p], np.asarray(vote, np.uint64)[p]
+    if propose_entries is not None:
+        app = cr["propose_result"] == abi.PROP_APPENDED
+        res["propose_first"] = np.where(app, cr["last_index"] - np.asarray(propose_entries, np.uint64)[p] +
+                                        np.uint64(1), 0)
+    x = (cr["flags"] & abi.CR_EXT) != 0
+    if x.any():
+        res[x] = np.asarray(ext, abi.RESULT)[cr["aux"][x].astype(np.int64)]
+    return res
 
 
 class Engine:
@@ -766,6 +822,55 @@ class Engine:
         n = self.max_peers - first if n is None else n
         out = np.zeros(n, abi.RESULT)
         _check(self.lib.gr_collect_results(self._h, first, out.ctypes.data, n), "gr_collect_results")
+        return out
+
+    def collect_updates(self, n=None, first=0, more_to_apply=True, every=False):
+        """gr_collect_updates: the peers of slots [first, first+n) that have a
+        pb.Update after the last device-resident pass (Peer.HasUpdate), as
+        (abi.CRESULT records by ascending slot, abi.RESULT ext records), copied out
+        of the engine's memory. Every reported peer's update state moves to its
+        State (the prevState half of Peer.Commit)."""
+        n = self.max_peers - first if n is None else n
+        flags = (abi.UPD_MORE_TO_APPLY if more_to_apply else 0) | (abi.UPD_EVERY if every else 0)
+        return self.collect_updates_flags(first, n, flags)
+
+    def collect_updates_flags(self, first, n, flags):
+        """collect_updates with the raw GR_UPD_* flag word."""
+        u = abi.Updates()
+        _check(self.lib.gr_collect_updates(self._h, first, n, flags, ctypes.byref(u)), "gr_collect_updates")
+        cr = np.zeros(u.n_results, abi.CRESULT)
+        rx = np.zeros(u.n_ext_results, abi.RESULT)
+        if u.n_results:
+            ctypes.memmove(cr.ctypes.data, u.results, u.n_results * abi.CRESULT.itemsize)
+        if u.n_ext_results:
+            ctypes.memmove(rx.ctypes.data, u.ext_results, u.n_ext_results * abi.RESULT.itemsize)
+        return cr, rx
+
+    def updates_last(self):
+        """gr_updates_last: the last collect_updates' record counts, the bytes it
+        copied device to host and, when per-pass timing was on, its two kernels'
+        event times (classify_ms, pack_ms, timed), as a dict."""
+        u = abi.UpdatesInfo()
+        _check(self.lib.gr_updates_last(self._h, ctypes.byref(u)), "gr_updates_last")
+        return {k: getattr(u, k) for k, _ in abi.UpdatesInfo._fields_ if k != "pad"}
+
+    def set_update_states(self, slots, recs):
+        """The peers' update states (abi.UPDATE_STATE, Peer.prevState) for a list of
+        engine slots (gr_set_update_states): a host that loads a group with
+        lastIndex > 0 sets it to the loaded {term, vote, committed}, as LaunchPeer does."""
+        slots = np.ascontiguousarray(slots, np.uint32)
+        recs = np.ascontiguousarray(recs, abi.UPDATE_STATE)
+        assert len(slots) == len(recs)
+        _check(self.lib.gr_set_update_states(self._h, slots.ctypes.data if len(slots) else None,
+                                             recs.ctypes.data if len(recs) else None, len(slots)),
+               "gr_set_update_states")
+
+    def get_update_states(self, slots):
+        slots = np.ascontiguousarray(slots, np.uint32)
+        out = np.zeros(len(slots), abi.UPDATE_STATE)
+        _check(self.lib.gr_get_update_states(self._h, slots.ctypes.data if len(slots) else None,
+                                             out.ctypes.data if len(out) else None, len(slots)),
+               "gr_get_update_states")
         return out
 
 

@@ -496,7 +496,8 @@ int gr_step_compact(gr_engine* e, const gr_cinbox* in, gr_coutbox* out);
  * gr_step_device, gr_load_* / gr_sync_*, gr_set_locals, gr_bind_routes,
  * gr_compact_log, gr_commit_update, gr_apply_config_change, gr_restore_remotes, gr_notify_applied,
  * gr_set_snapshot_recs, gr_get_snapshot_recs, gr_restored_snapshots, gr_set_cc_indexes,
- * gr_get_cc_indexes, gr_collect_results, gr_bind_nodes, gr_bind_targets,
+ * gr_get_cc_indexes, gr_collect_results, gr_collect_updates, gr_set_update_states,
+ * gr_get_update_states, gr_bind_nodes, gr_bind_targets,
  * gr_step_wire, gr_step_wire_compact, gr_step_wire_out, gr_step_compact_wire_out,
  * gr_space_cold_used) returns GR_ESTATE and changes nothing. */
 int gr_step_compact_begin(gr_engine* e, const gr_cinbox* in);
@@ -655,6 +656,106 @@ int gr_graph_replay(gr_graph* g, void* stream);
 void gr_graph_destroy(gr_graph* g);
 /* Copy per-peer results of the last device pass for peers [first, first+n). */
 int gr_collect_results(gr_engine* e, uint32_t first, gr_peer_result* out, size_t n);
+/*
+ * Updates out of the device-resident path: Peer.HasUpdate / Peer.GetUpdate
+ * (peer.go:212-241, 311-337) on the device. gr_collect_results is dense, one
+ * 168-byte record per slot whether or not the peer did anything;
+ * gr_collect_updates returns records only for the peers that have a pb.Update,
+ * as gr_step_compact returns results: a 24-byte gr_cresult, and the full
+ * gr_peer_result only where that cannot carry it.
+ *
+ * The update state: one gr_update_state per engine slot, Peer.prevState, in an
+ * allocation of its own made on first use and zeroed (the empty State, what
+ * LaunchPeer gives a new node, peer.go:96-100). gr_load_* / gr_sync_* of a group
+ * do not touch it: a host that loads a group with lastIndex > 0 sets the record
+ * to the loaded raftState() {term, vote, committed}, as LaunchPeer does. Slot
+ * rules of gr_set_update_states / gr_get_update_states are
+ * gr_set_snapshot_recs': out of range or listed twice is GR_ERANGE before
+ * anything is written, a call while a gr_step_compact_begin is pending GR_ESTATE.
+ *
+ * gr_update_class is the rule, for one peer after a pass (host-side, no engine;
+ * the device kernels run the same function): r its result record, log_applied
+ * and first_index_m1 as in gr_peer, prev its update state. A peer is reported
+ * (not GR_UPD_NONE) when
+ *   State changed      {term, vote, commit = committed} is not the empty State and
+ *                      differs from prev (peer.go:220-223);
+ *   entries to save    save_from != 0 (peer.go:231);
+ *   entries to apply   GR_UPD_MORE_TO_APPLY is set and committed + 1 >
+ *                      max(log_applied + 1, first_index_m1 + 1)
+ *                      (hasEntriesToApply, logentry.go:245-255);
+ *   ready to read      n_ready != 0 (peer.go:237);
+ *   engine conditions  escalation != 0, propose_result != GR_PROP_NONE or
+ *                      n_forwarded != 0: the host must always hear of these;
+ *   forced             GR_UPD_EVERY is set (tests, benchmarks, a full resync).
+ * Two conditions of HasUpdate are left out on purpose. len(r.msgs) > 0
+ * (peer.go:228) is none: on this path the messages stay in the out space.
+ * inmem.snapshot (peer.go:224) is none of its own: a restore moves committed, so
+ * the State condition reports the peer, and the host drains gr_restored_snapshots.
+ * A reported peer is GR_UPD_EXT, it needs its full gr_peer_result, when the
+ * compact record cannot carry it (an escalation, commit_lag >= 2^32, more than
+ * 255 entries to save), when n_ready or n_forwarded is not 0, or when term or
+ * vote differs from prev. The last rule is written against prev, not against the
+ * pass: a term that changed in a pass nobody collected (a graph replay of n
+ * passes) still arrives in full. Otherwise it is GR_UPD_COMPACT.
+ *
+ * gr_collect_updates speaks for the last device-resident pass over slots
+ * [first, first + n), as gr_collect_results does: there lane l steps peer l. The
+ * engine knows whether its lane rows are in that form: they are after gr_create
+ * (all zero: a collect before any pass sees no per-pass fields and reports from
+ * state alone), after gr_step_device and gr_graph_replay, and are not after
+ * gr_step, gr_step_compact* or gr_step_wire* (GR_ESTATE until the next device
+ * pass). Records are gr_cresult exactly as gr_step_compact defines them, peer =
+ * engine slot, ascending; GR_CR_EXT with aux = the index into ext_results,
+ * otherwise aux = esc_item. Emitting a record is the prevState half of
+ * Peer.Commit (peer.go:246-248): a reported peer whose State is not empty gets
+ * prev = State. The record also takes the lane's per-pass fields with it, as
+ * Peer.Commit drops msgs and readyToRead (peer.go:245, 249-251): the reported
+ * lane's result flags are cleared, so a second collect (or a gr_collect_results)
+ * before the next pass sees no propose_result, ready, append_from, forwarded
+ * counts or escalation for it and reports it only for what persists in state,
+ * entries still to save or to apply. The host then persists, applies and calls
+ * gr_commit_update; after that a collect is empty until the next pass.
+ * After a graph replay of n passes the per-pass fields (propose_result, ready,
+ * append_from, the forwarded counts) are the last pass's only; the fields derived
+ * from state (committed, last_index, save_from, term, vote) are cumulative.
+ * GR_EINVAL for a NULL argument, unknown flag bits or a range past max_peers;
+ * n == 0 is GR_OK with empty lists. The call waits for the device (passes may run
+ * on the caller's streams), then runs on the engine's stream; it cannot be
+ * captured. Device to host it copies two totals, then exactly 24 * n_results +
+ * 168 * n_ext_results bytes.
+ *
+ * gr_updates_last (benchmarks, tests): what the engine's last successful
+ * gr_collect_updates with n != 0 did: the records it returned, the bytes it
+ * copied device to host, counted at every copy it issued, and, when per-pass
+ * timing was on (gr_timing_begin), the event times of its two kernels in
+ * milliseconds (timed = 1). All zero before the first such call.
+ */
+#define GR_UPD_MORE_TO_APPLY 0x1 /* GetUpdate(moreEntriesToApply = true) */
+#define GR_UPD_EVERY 0x2
+enum gr_update_class_t { GR_UPD_NONE = 0, GR_UPD_COMPACT = 1, GR_UPD_EXT = 2 };
+typedef struct gr_update_state {
+  uint64_t term, vote, commit;
+} gr_update_state;
+typedef struct gr_updates { /* engine-owned pinned memory, valid until the next
+                               gr_collect_updates on this engine or gr_destroy */
+  gr_cresult* results;         /* ascending engine slot */
+  size_t n_results;
+  gr_peer_result* ext_results; /* in the order their records name them */
+  size_t n_ext_results;
+} gr_updates;
+int gr_set_update_states(gr_engine* e, const uint32_t* slots, const gr_update_state* recs, size_t n);
+int gr_get_update_states(gr_engine* e, const uint32_t* slots, gr_update_state* out, size_t n);
+int gr_collect_updates(gr_engine* e, uint32_t first, uint32_t n, uint32_t flags, gr_updates* out);
+int gr_update_class(const gr_peer_result* r, uint64_t log_applied, uint64_t first_index_m1,
+                    const gr_update_state* prev, uint32_t flags);
+typedef struct gr_updates_info {
+  uint64_t n_results, n_ext_results;
+  uint64_t bytes_down;
+  double classify_ms, pack_ms;
+  uint32_t timed;
+  uint32_t pad;
+} gr_updates_info;
+int gr_updates_last(gr_engine* e, gr_updates_info* out);
 /* Elections on the device (off by default; GR_ELECTIONS=1 in the environment
  * at gr_create turns them on). Off, every campaign, RequestVote, TimeoutNow and
  * candidate handler escalates (GR_ESC_ELECTION / GR_ESC_UNSUPPORTED). On, the
