@@ -340,7 +340,8 @@ int ensure_quiesce(gr_engine* e) {
     e->qmem = nullptr;
     return GR_ENOMEM;
   }
-  if (hipMemset(e->qmem, 0, bytes) != hipSuccess) {
+  if (hipMemsetAsync(e->qmem, 0, bytes, e->stream) != hipSuccess ||  // (as ensure_update_state)
+      hipStreamSynchronize(e->stream) != hipSuccess) {
     (void)hipFree(e->qmem);
     e->qmem = nullptr;
     return GR_EDEVICE;
@@ -360,7 +361,10 @@ int ensure_update_state(gr_engine* e) {
     e->upd_state = nullptr;
     return GR_ENOMEM;
   }
-  if (hipMemset(e->upd_state, 0, bytes) != hipSuccess) {
+  // on the engine's stream, and waited for: that stream is non-blocking, so a fill
+  // on the null stream is not ordered before the kernels that use the records next
+  if (hipMemsetAsync(e->upd_state, 0, bytes, e->stream) != hipSuccess ||
+      hipStreamSynchronize(e->stream) != hipSuccess) {
     (void)hipFree(e->upd_state);
     e->upd_state = nullptr;
     return GR_EDEVICE;

@@ -318,9 +318,10 @@ class Population:
     The counters (self.count) are computed from the reference side's records
     alone, so they do not depend on the code under test."""
 
-    def __init__(self, be, peers, snap, G, R):
+    def __init__(self, be, peers, snap, G, R, updates=False, drain_after=False):
         from dragonboat_amd import populations as P
         self.be, self.G, self.R, self.S, self.n = be, G, R, R, G * R
+        self.updates, self.drain_after = updates, drain_after
         self.topo = P.Topology(G, R)
         self.all = np.arange(self.n, dtype=np.uint32)
         self.msgs = np.zeros(0, abi.MESSAGE)  # the next inbox (receiver peer, sender slot)
@@ -339,6 +340,7 @@ class Population:
             self.state, _, _ = hostlane_step(peers, None, None, self.S)
             self.snap, self.cc = self.refsnap.copy(), self.refcc.copy()
             self.ref = self.state.copy()
+            self._launch_updates()
             return
         from dragonboat_amd.engine import Engine
         self.eng = Engine(self.n, self.S, elections=True, snapshots=True, config_entries=True)
@@ -363,6 +365,103 @@ class Population:
                 slot[self.in_pos[j, ok].astype(np.int64)] = j
             self.inv = (peer, slot)
             self.dirty = False  # the space the next pass reads must be re-encoded
+        self._launch_updates()
+
+    # -- updates=True: the host learns what to persist, apply and answer from
+    # gr_collect_updates alone (INTEGRATION.md "Updates out of the device-resident path")
+    def _launch_updates(self):
+        """LaunchPeer with lastIndex > 0: the update states are the loaded
+        raftState(); the host's applied index is the loaded one."""
+        if not self.updates:
+            return
+        import updates_common as UC
+        assert self.be in ("cpu", "dev"), "gr_collect_updates speaks for device-resident passes"
+        self.upd = UC.RefUpdates(self.n)
+        st = self.upd.launch(self.ref)
+        if self.be == "dev":
+            self.eng.set_update_states(self.all, st)
+        self.happ = self.ref["log_applied"].copy()  # the applied index the host holds
+        self.reported = np.zeros(0, abi.RESULT)    # the last collect's records, expanded
+        self.upd_counts = []  # per pass, from the reference side's records: (reported, ext records, restored peers)
+
+    def _collect(self, k, loc, before, res, st, rres, rst, rrest, rest):
+        """The collect after pass k, before anything is reloaded. The reference
+        for it is the reference side's own pass: rres / rst (ref_step), through the
+        rule of updates_common. On "dev" gr_collect_updates with the default flags;
+        on "cpu" the same call emulated by gr_update_class over the host lane's
+        results. Leaves the reported peers' records in self.reported."""
+        import updates_common as UC
+        from dragonboat_amd.engine import expand_updates, update_class
+        n = self.n
+        assert len(res) == n and np.array_equal(res["peer"], self.all), "every peer takes a local input, in peer order"
+        cls = UC.ref_classes(rres, rst["log_applied"], rst["first_index_m1"], self.upd.prev, UC.MORE)
+        reported = cls != abi.UPD_NONE
+        who = np.unique(rrest["peer"]).astype(np.int64)
+        turned = (before["state"] != abi.LEADER) & (rst["state"] == abi.LEADER)
+        uc = parity.update_commits(rst)
+        owes = (uc["stable_log_to"] != 0) | (uc["applied_to"] != 0)
+        restored = np.zeros(n, bool)
+        restored[who] = True
+        # of the reference itself: the rule, which leaves inmem.snapshot out, loses none of these
+        for what, m in (("restored", restored), ("promoted", turned), ("with something to commit", owes)):
+            assert reported[m].all(), f"pass {k}: {what} peers the rule does not report: {np.nonzero(m & ~reported)[0][:8]}"
+        self.upd_counts.append((int(reported.sum()), int(np.sum(cls == abi.UPD_EXT)), len(who)))
+        prev = self.upd.prev.copy()
+        if self.be == "cpu":
+            got = update_class(res, st["log_applied"], st["first_index_m1"], prev)
+            rep, rcls = self.upd.collect(rres, rst, 0, n, UC.MORE)
+            assert np.array_equal(np.nonzero(got)[0], rep), \
+                f"pass {k}: reported {sorted(set(np.nonzero(got)[0].tolist()) ^ set(rep.tolist()))[:8]}"
+            assert np.array_equal(got[rep], rcls), f"pass {k}: classes"
+            self.reported = res[rep]
+            return
+        if not self.drain_after:
+            prom = self.eng.promotions()
+        cr, rx, _, _ = UC.check_collect(self.eng, self.upd, n, propose_entries=loc["propose_entries"], dense=rres,
+                                        state=rst)
+        assert len(cr) == int(reported.sum()) and len(rx) == self.upd_counts[-1][1]
+        if self.drain_after:  # the collect cleared LR_RFLAGS; it takes nothing from the two lists
+            prom, rest = self.eng.promotions(), self.eng.restored_snapshots()
+        assert _rest_key(rest) == _rest_key(rrest), f"pass {k}: restored {(_rest_key(rest)[:4], _rest_key(rrest)[:4])}"
+        assert sorted(prom["peer"].tolist()) == np.nonzero(turned)[0].tolist(), f"pass {k}: promotions"
+        for r in prom:  # the empty entry: the first of the new leader's term
+            g, i, t = rst[int(r["peer"])], int(r["noop_index"]), int(r["term"])
+            assert t == int(g["term"]) and CE._term_at(g, i) == t and CE._term_at(g, i - 1) != t, (k, r)
+        self.reported = expand_updates(cr, rx, prev["term"], prev["vote"], loc["propose_entries"])
+
+    def _commit_reported(self, rrest):
+        """gr_commit_update and gr_notify_applied from the records alone, to the
+        reported slots and to no others. An escalated peer was reloaded with the
+        record of its whole pass: the host commits what that record holds."""
+        r = self.reported
+        slots = r["peer"].astype(np.int64)
+        # the RSM recovered from the snapshots of the restored list
+        np.maximum.at(self.happ, rrest["peer"].astype(np.int64), rrest["index"])
+        if len(slots) == 0:
+            return
+        own = self.ref[slots]  # the host's own log: the terms it persisted
+        uc = np.zeros(len(slots), abi.UPDATE_COMMIT)
+        save = r["save_from"] != 0
+        uc["stable_log_to"] = np.where(save, r["last_index"], 0)
+        uc["stable_log_term"] = np.where(
+            save, own["run_term"][np.arange(len(own)), np.maximum(own["n_runs"].astype(np.int64) - 1, 0)], 0)
+        committed = r["committed"].copy()
+        esc = r["escalation"] != 0
+        if esc.any():
+            uc[esc] = parity.update_commits(own[esc])
+            uc["applied_to"][esc] = 0
+            committed[esc] = own["committed"][esc]
+        above = committed > self.happ[slots]
+        uc["applied_to"] = np.where(above, committed, 0)
+        self.happ[slots] = np.where(above, committed, self.happ[slots])
+        if self.be == "cpu":
+            rc, stt = host_commit_update(self.state, slots, uc, self.S)
+            assert rc == 0, (rc, stt[stt != 0][:4])
+            self.state["applied"][slots] = committed
+        else:
+            rc, stt = self.eng.commit_update(slots.astype(np.uint32), uc)
+            assert rc == 0, (rc, stt[stt != 0][:4])
+            self.eng.notify_applied(slots.astype(np.uint32), committed)
 
     # -- one pass on the engine side: (state, snap, cc, the next inbox's records, results, restored)
     def _engine_pass(self, loc):
@@ -388,8 +487,8 @@ class Population:
             pos = nxt["peer"].astype(np.int64)
             nxt["peer"] = self.inv[0][pos].astype(np.uint32)
             nxt["slot"] = self.inv[1][pos].astype(np.uint8)
-        return (eng.sync(self.n), eng.get_snapshot_recs(self.all), eng.get_cc_indexes(self.all), nxt, res,
-                eng.restored_snapshots())
+        rest = None if self.updates and self.drain_after else eng.restored_snapshots()  # None: drained after the collect
+        return eng.sync(self.n), eng.get_snapshot_recs(self.all), eng.get_cc_indexes(self.all), nxt, res, rest
 
     def _encode(self, msgs, space):
         buf = np.zeros(self.eng.space_bytes(1, self.positions, self.depth), np.uint8)
@@ -422,8 +521,10 @@ class Population:
         rst, rsnap, rcc, rout, rres, rrest, panic = ref_step(self.ref, self.refsnap, self.refcc, self.msgs, loc,
                                                               self.S, lim)
         assert np.all(panic < 0), (k, np.nonzero(panic >= 0)[0][:4])
-        compare_pass(self.S, (st, snap, cc, nxt, res, rest),
+        compare_pass(self.S, (st, snap, cc, nxt, res, rrest if rest is None else rest),
                      (rst, rsnap, rcc, self.topo.route_messages(rout), rres, rrest), f"pass {k}: ")
+        if self.updates:
+            self._collect(k, loc, before, res, st, rres, rst, rrest, rest)
         esc = res[res["escalation"] != 0]
         for r in esc:
             nm = abi.ESC_NAMES[r["escalation"]]
@@ -439,6 +540,12 @@ class Population:
             self._load(idx, rst[idx], rcc[idx], rsnap[idx])
             if self.be == "dev":
                 self.dirty = True
+            if self.updates:  # reloaded: the update state is the State the host already handed on
+                hs = np.zeros(len(idx), abi.UPDATE_STATE)
+                hs["term"], hs["vote"], hs["commit"] = rst["term"][idx], rst["vote"][idx], rst["committed"][idx]
+                self.upd.prev[idx] = hs
+                if self.be == "dev":
+                    self.eng.set_update_states(idx.astype(np.uint32), hs)
         self._count(before, rst, rout, rrest)
         self.ref, self.refsnap, self.refcc = rst, rsnap, rcc
         out = self.topo.route_messages(rout)
@@ -487,8 +594,10 @@ class Population:
                 assert len(self.eng.restored_snapshots()) == 0
             assert rc == 0 and not stt.any(), (rc, stt)
         uc = parity.update_commits(self.ref)
-        new = CE.ref_commit_all(self.ref, self.S)
-        if self.be == "cpu":
+        new = CE.ref_commit_all(self.ref, self.S)  # the reference side commits every peer, reported or not
+        if self.updates:
+            self._commit_reported(rrest)
+        elif self.be == "cpu":
             rc, stt = host_commit_update(self.state, self.all, uc, self.S)
             assert rc == 0, (rc, stt[stt != 0][:4])
             self.state["applied"] = new["applied"]

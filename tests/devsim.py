@@ -239,7 +239,12 @@ class DeviceLockstep:
         self._encode(msgs, self.spaces[self.k % 2])
         self.msgs = msgs
 
-    def step(self, loc, drop_fn=None):
+    def step(self, loc, drop_fn=None, collect=None):
+        """collect(o): called with the oracle's pass (o["results"] by peer,
+        o["mid"] the records at the device prefix, o["esc_mask"]) after the pass's
+        parity checks and before an escalated peer is reloaded or the space
+        re-encoded: where a host collects its updates, before it hands an
+        escalated group over."""
         import torch
         k = self.k
         loc = np.asarray(loc, abi.LOCAL)
@@ -275,6 +280,9 @@ class DeviceLockstep:
         st["commits"] += int(np.sum(dev["committed"] > dev0["committed"]))
         st["ready"] += int(res["n_ready"].sum())
         st["msgs"] += len(got)
+        if collect is not None:
+            o["limits"], o["device_results"] = lim, res  # which item each escalated peer stopped before
+            collect(o)
         full = self.pop.export()
         assert self.pop.representable().all(), "a peer outgrew its gr_peer record"
         nxt = self._route(o["msgs"])

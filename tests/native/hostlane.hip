@@ -44,6 +44,20 @@ static uint32_t g_hint_salt = 0;  // varies the drawn wave hints from call to ca
 static bool g_true_hints = false;  // hl_true_hints: every wave gets the device's hint (diagnostics)
 static bool g_force_unhinted = false;  // hl_force_unhinted: every wave unhinted, split passes (lane_closed_form)
 
+// hl_update_fields: the update fields of every lane of the last hl_step, both
+// ways (kUfWords words a lane, UpdateFields' members in order), the lanes' result
+// flags, and whether lane l stepped peer l throughout
+constexpr uint32_t kUfWords = 9;
+static std::vector<uint64_t> g_uf_result, g_uf_lane;
+static std::vector<uint16_t> g_uf_rflags;
+static bool g_uf_by_slot = false;
+
+void uf_words(const UpdateFields& f, uint64_t* w) {
+  const uint64_t v[kUfWords] = {f.term,       f.vote,           f.committed, f.last_index, f.save_from,
+                                f.escalation, f.propose_result, f.n_ready,   f.n_forwarded};
+  memcpy(w, v, sizeof(v));
+}
+
 template <int S>
 void run_lanes(const StepParams& kp) {
   // the kernel's two passes: the steady-state subset first, the general lane
@@ -282,7 +296,36 @@ extern "C" int hl_step(uint32_t slots, uint64_t max_entry_size, gr_peer* peers, 
   if (results) {
     for (uint32_t l = 0; l < nl; ++l) results[l] = make_result(ln, st, l, pk.peers[l]);
   }
+  // lane_update_fields indexes lane and state rows by one number, as the
+  // device-resident path does: it stands for make_result only where lane l = peer l
+  g_uf_by_slot = nl == n_peers;
+  for (uint32_t l = 0; l < nl && g_uf_by_slot; ++l) g_uf_by_slot = pk.peers[l] == l;
+  g_uf_result.assign((size_t)nl * kUfWords, 0);
+  g_uf_lane.assign((size_t)nl * kUfWords, 0);
+  g_uf_rflags.assign(nl, 0);
+  for (uint32_t l = 0; l < nl && g_uf_by_slot; ++l) {
+    uf_words(update_fields(make_result(ln, st, l, l)), &g_uf_result[(size_t)l * kUfWords]);
+    uf_words(lane_update_fields(ln, st, l), &g_uf_lane[(size_t)l * kUfWords]);
+    g_uf_rflags[l] = (uint16_t)(ln.u8(LR_RFLAGS)[l] | (h_cl(st.u64(SR_HDR)[l]) ? 0x100u : 0u));
+  }
   return GR_OK;
+}
+
+// After an hl_step in which lane l stepped peer l for all l: for every lane,
+// update_fields(make_result(..)) into from_result and lane_update_fields(..) into
+// from_lane, 9 words a lane (UpdateFields' members in order), and the lane's
+// LR_RFLAGS byte with bit 8 set where the header carries the commit lag. Returns
+// the number of lanes, GR_ESTATE when some lane stepped another peer (the
+// shortcut then reads the wrong lane rows), GR_ECAPACITY when cap is too small.
+extern "C" int hl_update_fields(uint64_t* from_result, uint64_t* from_lane, uint16_t* rflags, uint32_t cap) {
+  if (!g_uf_by_slot) return GR_ESTATE;
+  const uint32_t nl = (uint32_t)g_uf_rflags.size();
+  if (!from_result || !from_lane || !rflags) return GR_EINVAL;
+  if (cap < nl) return GR_ECAPACITY;
+  memcpy(from_result, g_uf_result.data(), g_uf_result.size() * sizeof(uint64_t));
+  memcpy(from_lane, g_uf_lane.data(), g_uf_lane.size() * sizeof(uint64_t));
+  for (uint32_t l = 0; l < nl; ++l) rflags[l] = g_uf_rflags[l];
+  return (int)nl;
 }
 
 // gr_commit_update on records: the same commit_marks (gr_host.h) the device runs.

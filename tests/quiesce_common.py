@@ -66,9 +66,10 @@ class QuiesceLockstep(devsim.DeviceLockstep):
                     out.append(r)
         return np.concatenate(out) if out else np.zeros(0, abi.MESSAGE)
 
-    def step(self, loc=None, drop_fn=None, tick_all=None):
+    def step(self, loc=None, drop_fn=None, tick_all=None, collect=None):
         """tick_all=(ticks, seed): bind with gr_tick_all; else gr_set_locals(loc).
-        loc carries raw LocalTick counts either way."""
+        loc carries raw LocalTick counts either way. collect(o): as
+        DeviceLockstep.step, after the parity checks and before any reload."""
         import torch
         k = self.k
         if tick_all is not None:
@@ -148,6 +149,10 @@ class QuiesceLockstep(devsim.DeviceLockstep):
             st["esc_reasons"][nm] = st["esc_reasons"].get(nm, 0) + 1
         st["commits"] += int(np.sum(dev["committed"] > dev0["committed"]))
         st["msgs"] += len(got)
+        if collect is not None:
+            o["limits"], o["device_results"] = lim, res  # which item each escalated peer stopped before
+            collect(o)
+            full = self.pop.export()  # the callback may have committed on the oracle
         nxt = self._route(np.concatenate([self._quiesce_msgs(full_send, full), o["msgs"]]))
         n_full = len(nxt)
         if drop_fn is not None:

@@ -448,14 +448,17 @@ def _population(G, R, seed):
     return peers, snap
 
 
-def live_all(be, G, seed=31):
+def live_all(be, G, seed=31, updates=False, drain_after=False):
     """G groups x 5 with every switch on, scripted (see the tests' docstring).
-    Returns the finished Population and the committed indexes after every pass."""
+    Returns the finished Population and the committed indexes after every pass.
+    updates: the host is driven by gr_collect_updates alone
+    (all_switches_common.Population); drain_after: it drains the restored and the
+    promotion list after the collect, not before it."""
     from dragonboat_amd import populations as P
     R = 5
     n = R * G
     peers, snap = _population(G, R, seed)
-    pop = C.Population(be, peers, snap, G, R)
+    pop = C.Population(be, peers, snap, G, R, updates=updates, drain_after=drain_after)
     kind = _kinds(G)
     grp = np.arange(n) % G
     rep = np.arange(n) // G
@@ -574,3 +577,48 @@ def test_live_all_gpu(gpu, monkeypatch, be, G):
 
 for _t in (test_live_all_hostlane_192, test_live_all_hostlane_200, test_live_all_gpu):
     _t.__doc__ = LIVE_DOC
+
+
+# ---------------------------------------------------------------- the same, the host driven by the collect alone
+# Per pass, from the reference side's records (ref_step's results and peer
+# records through updates_common.ref_classes, prevState mirrored from the loaded
+# State): reported peers, ext records, restored peers. Per 24 groups (G = 192: x 8)
+# and per 25 (G = 200: x 8): of 120 / 125 peers.
+UPD_REPORTED = {192: [960, 912, 768, 960, 768, 960, 864, 960, 696, 888, 672, 864, 672, 864, 864, 864, 888, 864, 864, 864],
+                200: [1000, 950, 800, 1000, 800, 1000, 900, 1000, 725, 925, 700, 900, 700, 900, 900, 900, 925, 900, 900,
+                      900]}
+UPD_EXT = {192: {8: 72, 9: 288}, 200: {8: 75, 9: 300}}
+UPD_RESTORED = {192: {1: 144, 3: 48, 16: 24}, 200: {1: 150, 3: 50, 16: 25}}
+
+
+def check_update_counts(pop, G):
+    """The reference's own counts per pass (Population._collect computes them
+    from rres / rst alone) against the table; the engine's equal them pass by pass
+    (asserted at every collect)."""
+    got = pop.upd_counts
+    print("updates per pass (reported, ext, restored)", pop.be, G, got)
+    assert len(got) == PASSES
+    assert [c[0] for c in got] == UPD_REPORTED[G]
+    assert {k: c[1] for k, c in enumerate(got) if c[1]} == UPD_EXT[G]
+    assert {k: c[2] for k, c in enumerate(got) if c[2]} == UPD_RESTORED[G]
+
+
+@pytest.mark.parametrize("G", [192, 200])
+def test_live_all_updates_hostlane(built, G):
+    """live_all with the host driven by the collect alone, on the host lane (the
+    collect emulated by gr_update_class over the host lane's results): after every
+    pass the rule of updates_common.ref_classes runs over the reference side's own
+    results and records, and gr_commit_update / gr_notify_applied go to the
+    reported peers only, with stable_log_to and applied_to taken from the records.
+    The reference side still commits every peer, so a peer the rule failed to
+    report shows as a saved_to / log_applied difference in the next pass's
+    comparison. Asserted of the reference in every pass: every restored peer,
+    every promoted peer and every peer parity.update_commits has something to
+    commit for is reported ("a restore moves committed, so the State condition
+    reports it"; "a host that commits only the reported slots loses nothing").
+    The counts per pass are the reference's, recomputed here, and equal the
+    table derived on the reference side alone (UPD_REPORTED, UPD_EXT,
+    UPD_RESTORED)."""
+    pop, committed = live_all("cpu", G, updates=True)
+    check_live_all(pop, committed, G)
+    check_update_counts(pop, G)

@@ -156,3 +156,37 @@ def test_expand_updates_follows_cresult_rules():
     assert res["committed"].tolist() == [8, 2**32 + 9, 0] and res["save_from"].tolist() == [0, 2**32 + 7, 0]
     assert res["term"].tolist() == [102, 105, 9] and res["vote"].tolist() == [202, 205, 0]
     assert res["propose_first"].tolist() == [0, 2**32 + 8, 0] and res["n_ready"].tolist() == [0, 0, 2]
+
+
+# The cold start of tests/test_elections_gpu.py (elections_common.cold_peers(G, 3,
+# 21), 40 passes of one tick) through the oracle alone, the rule over its records,
+# the reported peers committed after every pass: reported peers and ext records
+# per pass. tests/test_updates_switches_gpu.py requires the same of the device.
+COLD_REPORTED = {
+    200: [600, 21, 49, 72, 99, 160, 179, 207, 197, 213, 177, 146, 101, 76, 47, 23, 15, 3, 3, 2, 0, 0, 0, 0, 0, 0, 1, 2,
+          1, 2, 1, 2, 0, 0, 0, 0, 0, 0, 0, 0],
+    320: [960, 42, 70, 120, 164, 220, 265, 308, 320, 317, 306, 241, 204, 123, 94, 34, 19, 8, 5, 2, 0, 1, 2, 1, 2, 1, 2,
+          0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0]}
+COLD_EXT = {
+    200: [4, 21, 45, 51, 50, 90, 84, 71, 60, 56, 28, 21, 10, 1, 6, 2, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 2, 0, 0, 0, 0, 0,
+          0, 0, 0, 0, 0, 0, 0],
+    320: [12, 42, 58, 79, 94, 100, 113, 129, 113, 92, 78, 25, 13, 6, 4, 2, 0, 0, 0, 0, 0, 1, 2, 0, 0, 0, 0, 0, 0, 0, 0,
+          0, 0, 0, 0, 0, 0, 0, 0, 0]}
+
+
+def cold_locals(G, k):
+    from dragonboat_amd import populations as P
+    return P.propose_locals(3 * G, np.zeros(0, np.int64), seed=21, pass_index=k, ticks=1)
+
+
+@pytest.mark.parametrize("G", [200, 320])
+def test_cold_start_counts_of_the_oracle(built, G):
+    """What the device's collects are held to in test_updates_switches_gpu.py,
+    of the reference alone: the counts per pass, a pass that reports nothing and
+    one that reports more than a quarter of the peers. Pass 0 reports every peer
+    (the loaded groups have entries to apply); the update states are the loaded
+    State, so only the peers whose term moves in it are EXT."""
+    import elections_common as EC
+    counts = UC.oracle_collect_counts(EC.cold_peers(G, 3, 21), G, 3, 40, lambda k: cold_locals(G, k))
+    assert [c[0] for c in counts] == COLD_REPORTED[G] and [c[1] for c in counts] == COLD_EXT[G]
+    assert 0 in COLD_REPORTED[G][1:] and max(COLD_REPORTED[G][1:]) > 3 * G // 4
